@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path of BASELINE.json on MI355X: seekable-zstd frame decode (GiB/s of decompressed data).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2] [--dump-outputs DIR] [--full]
 
 A step = one pass of the decode hot path over one batch of synthetic frames that are already resident in
 HBM (compressed payload + seek-table offsets in, decompressed bytes out, Content_Checksums verified).
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else
+the line can carry: the parity checks against the generator's bytes, the encode legs, the CPU baselines, the
+reference-made archives, the kernel rooflines, end to end, configs[0], the seeks and (N > 1) the gather leg.
 Workloads (BASELINE.json configs, generator of SURVEY.md 8d):
   c3 (default)  configs[2]: 4 GiB per GPU = 2048 frames x 2 MiB, level 1, XXH64 checksums on  -- the
                 configuration the north-star target is quoted on; weak scaling: every rank owns its own
@@ -28,6 +31,7 @@ import numpy as np  # noqa: E402
 
 FRAME = 2 << 20
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable
+DUMP_SAMPLES = 1 << 23         # --dump-outputs: decoded bytes sampled at fixed, seeded positions (32 MiB as float32)
 
 
 _SHM = None
@@ -621,6 +625,25 @@ def seek_leg(eng, data, zk, z64, nbytes, trials, fsz=65536):
     return out
 
 
+def dump_positions(dsize):
+    """The fixed, seeded byte positions of decoded_sample.npy (the same for every run of a workload)."""
+    return np.sort(np.random.default_rng(0x5EED0D).integers(0, dsize, min(DUMP_SAMPLES, dsize), dtype=np.int64))
+
+
+def dump_outputs(dirname, d_out, d_st, dsize, nframes):
+    """What the timed path hands its caller after its last step, for comparing two builds output for output: the decoded bytes at
+    DUMP_SAMPLES fixed, seeded positions, every frame's byte sum (the whole output, 2 MiB frames) and the per-frame statuses."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_positions(dsize)
+    sample = d_out[torch.from_numpy(idx).to(d_out.device)].cpu().numpy()
+    frames = d_out[:dsize].view(nframes, -1)
+    sums = torch.cat([frames[i:i + 64].sum(1, dtype=torch.int64) for i in range(0, nframes, 64)])     # 64 frames at a time: sum() widens a copy
+    np.save(os.path.join(dirname, "decoded_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(dirname, "decoded_frame_sums.npy"), sums.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "frame_status.npy"), d_st[:nframes].cpu().numpy().astype(np.float32))
+
+
 def dry_run(args, rank, world):
     """The N > 1 launch contract without a GPU (CI here: gloo): RANK / WORLD_SIZE / MASTER_* from the environment, the process
     group, barriers, max-over-ranks timing, the shard + gather leg (zeekstd_amd/parallel.py) and rank 0's single JSON line.
@@ -658,7 +681,7 @@ def dry_run(args, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         dist.barrier(); tg = time.perf_counter()
         out, table = parallel.encode_sharded(StoredFrames(), d_src, fsz, 1, False, root=0)
         dist.barrier()
@@ -708,6 +731,12 @@ def main():
     ap.add_argument("--gather-only", action="store_true", help="N > 1: one untimed-quality decode step, then the gather leg (what a scaling run is asked about first)")
     ap.add_argument("--archive", default="auto", choices=["auto", "gpu", "libzstd"],
                     help="who compresses the archive that is decoded: the GPU encoder (default for c3) or CPU libzstd (default for c2)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy: a seeded sample of the "
+                         "decoded bytes, every frame's byte sum and the per-frame statuses")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: parity checks, encode legs, CPU baselines, reference-made archives, rooflines, "
+                         "end to end, configs[0], seeks, the gather leg (N > 1); the --no-* options trim it")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -722,21 +751,22 @@ def main():
     if one_gpu:
         local_rank = 0                                     # every rank on device 0
     if args.gather_only:
-        args.steps, args.warmup = 1, 1
+        args.steps, args.warmup, args.full = 1, 1, True
         args.no_cpu_baseline = args.no_seek = args.no_e2e = args.no_c1 = args.no_ref_archive = True
     if args.dry_run:
         return dry_run(args, rank, world)
 
     # ---- untimed setup on the host cores (before any HIP initialisation: workers are forked)
-    cores = os.cpu_count() or 8
+    full = args.full
+    cores = len(os.sched_getaffinity(0)) or 8                 # the cores this process may run on, not the machine's
     workers = 1 if args.no_fork else max(1, min(64, cores // max(1, world) - 1))
     use_gpu_archive = args.archive == "gpu" or (args.archive == "auto" and args.workload == "c3")
     t0 = time.time()
     # a reference-made archive of the same input is prepared too (single-GPU runs): its decode rate is reported beside the
     # headline, because archives written by zeekstd's own CPU Encoder are what a drop-in user decodes first
-    want_ref_archive = (not use_gpu_archive) or (world == 1 and not args.no_ref_archive)
+    want_ref_archive = (not use_gpu_archive) or (full and world == 1 and not args.no_ref_archive)
     data, z_comp, z_frames, hashes = build_inputs(rank * nframes, nframes, level, cks, workers, want_ref_archive, rank, args.cache)
-    do_seek = rank == 0 and world == 1 and not args.no_seek
+    do_seek = full and rank == 0 and world == 1 and not args.no_seek
     z64 = None
     if do_seek and want_ref_archive and z_comp:           # the reference-made 64 KiB-frame archive of configs[3] (forked workers: before HIP)
         z64 = libzstd_archive_parallel(np.asarray(data), 65536, level, True, workers)
@@ -785,52 +815,53 @@ def main():
         torch.cuda.synchronize()                                # torch's fills have landed before the engine's own queue writes the same buffers
         nf, csize = eng.encode_frames_dev(d_src, dsize, FRAME, level, cks, d_comp, cap, d_cs, d_ds)      # warm-up + the archive
         torch.cuda.synchronize()
-        te = []
-        for _ in range(max(3, args.steps // 2)):
-            t = time.perf_counter()
+        if full:
+            te = []
+            for _ in range(max(3, args.steps // 2)):
+                t = time.perf_counter()
+                eng.encode_frames_dev(d_src, dsize, FRAME, level, cks, d_comp, cap, d_cs, d_ds)
+                te.append(time.perf_counter() - t)
+            eng.set_profiling(True)
             eng.encode_frames_dev(d_src, dsize, FRAME, level, cks, d_comp, cap, d_cs, d_ds)
-            te.append(time.perf_counter() - t)
-        eng.set_profiling(True)
-        eng.encode_frames_dev(d_src, dsize, FRAME, level, cks, d_comp, cap, d_cs, d_ds)
-        ek = eng.kernel_times()
-        eng.set_profiling(False)
+            ek = eng.kernel_times()
+            eng.set_profiling(False)
+            enc_info = {"value": round(dsize / min(te) / 2**30, 2), "unit": "GiB/s", "ratio": round(dsize / csize, 3),
+                        "ms": round(min(te) * 1e3, 2), "kernel_ms": {k: round(v, 3) for k, v in ek.items()},
+                        "calls_ms": _stats_ms(te),
+                        "roofline": roofline_of(ek, dsize + csize, min(te) * 1e3, "kernels", nframes == 2048)}
+            # (r6) the same input at the reference CLI's default level (cli/src/args.rs:192): dense far history (zk_k_enc_dense_cand); its first
+            # eight frames decoded and compared with the input.  Not the headline: one line of the report.
+            if rank == 0 and world == 1 and level == 1 and not args.no_e2e:
+                try:
+                    d_comp3 = torch.empty(cap + 64, dtype=torch.uint8, device=dev)
+                    d_cs3 = torch.zeros(nframes, dtype=torch.int32, device=dev)
+                    torch.cuda.synchronize()
+                    _, csize3 = eng.encode_frames_dev(d_src, dsize, FRAME, 3, cks, d_comp3, cap, d_cs3, d_ds)
+                    t3 = []
+                    for _ in range(2):
+                        t = time.perf_counter()
+                        eng.encode_frames_dev(d_src, dsize, FRAME, 3, cks, d_comp3, cap, d_cs3, d_ds)
+                        t3.append(time.perf_counter() - t)
+                    eng.set_profiling(True)
+                    eng.encode_frames_dev(d_src, dsize, FRAME, 3, cks, d_comp3, cap, d_cs3, d_ds)
+                    ek3 = eng.kernel_times()
+                    eng.set_profiling(False)
+                    nchk = min(8, nframes)
+                    c3 = np.zeros(nchk + 1, np.int64); c3[1:] = np.cumsum(d_cs3[:nchk].cpu().numpy().astype(np.int64))
+                    d3 = np.arange(nchk + 1, dtype=np.int64) * FRAME
+                    o3 = torch.empty(nchk * FRAME + 64, dtype=torch.uint8, device=dev)
+                    s3 = torch.zeros(nchk, dtype=torch.int32, device=dev)
+                    eng.decode_frames_dev(d_comp3, int(c3[-1]), torch.from_numpy(c3).to(dev), torch.from_numpy(d3).to(dev), 0, nchk, o3, nchk * FRAME, True, s3)
+                    ok3 = bool(torch.equal(o3[:nchk * FRAME], d_src[:nchk * FRAME])) and int(s3.abs().sum().item()) == 0
+                    enc_info["level_3"] = {"value": round(dsize / min(t3) / 2**30, 2), "unit": "GiB/s", "ratio": round(dsize / csize3, 3), "ms": round(min(t3) * 1e3, 2),
+                                           "kernel_ms": {k: round(v, 3) for k, v in ek3.items() if "enc" in k}, "first_frames_round_trip": ok3,
+                                           "roofline": roofline_of({k: v for k, v in ek3.items() if "enc" in k}, dsize + csize3, min(t3) * 1e3, None, False)}
+                    del d_comp3, d_cs3, o3
+                except Exception as ex:                                   # noqa: BLE001  (a leg of the report, not the run)
+                    enc_info["level_3"] = {"error": f"{type(ex).__name__}: {ex}"}
         cs = d_cs.cpu().numpy().astype(np.uint64)
         frames = [(int(c), FRAME) for c in cs]
         comp = None
-        enc_info = {"value": round(dsize / min(te) / 2**30, 2), "unit": "GiB/s", "ratio": round(dsize / csize, 3),
-                    "ms": round(min(te) * 1e3, 2), "kernel_ms": {k: round(v, 3) for k, v in ek.items()},
-                    "calls_ms": _stats_ms(te),
-                    "roofline": roofline_of(ek, dsize + csize, min(te) * 1e3, "kernels", nframes == 2048)}
-        # (r6) the same input at the reference CLI's default level (cli/src/args.rs:192): dense far history (zk_k_enc_dense_cand); its first
-        # eight frames decoded and compared with the input.  Not the headline: one line of the report.
-        if rank == 0 and world == 1 and level == 1 and not args.no_e2e:
-            try:
-                d_comp3 = torch.empty(cap + 64, dtype=torch.uint8, device=dev)
-                d_cs3 = torch.zeros(nframes, dtype=torch.int32, device=dev)
-                torch.cuda.synchronize()
-                _, csize3 = eng.encode_frames_dev(d_src, dsize, FRAME, 3, cks, d_comp3, cap, d_cs3, d_ds)
-                t3 = []
-                for _ in range(2):
-                    t = time.perf_counter()
-                    eng.encode_frames_dev(d_src, dsize, FRAME, 3, cks, d_comp3, cap, d_cs3, d_ds)
-                    t3.append(time.perf_counter() - t)
-                eng.set_profiling(True)
-                eng.encode_frames_dev(d_src, dsize, FRAME, 3, cks, d_comp3, cap, d_cs3, d_ds)
-                ek3 = eng.kernel_times()
-                eng.set_profiling(False)
-                nchk = min(8, nframes)
-                c3 = np.zeros(nchk + 1, np.int64); c3[1:] = np.cumsum(d_cs3[:nchk].cpu().numpy().astype(np.int64))
-                d3 = np.arange(nchk + 1, dtype=np.int64) * FRAME
-                o3 = torch.empty(nchk * FRAME + 64, dtype=torch.uint8, device=dev)
-                s3 = torch.zeros(nchk, dtype=torch.int32, device=dev)
-                eng.decode_frames_dev(d_comp3, int(c3[-1]), torch.from_numpy(c3).to(dev), torch.from_numpy(d3).to(dev), 0, nchk, o3, nchk * FRAME, True, s3)
-                ok3 = bool(torch.equal(o3[:nchk * FRAME], d_src[:nchk * FRAME])) and int(s3.abs().sum().item()) == 0
-                enc_info["level_3"] = {"value": round(dsize / min(t3) / 2**30, 2), "unit": "GiB/s", "ratio": round(dsize / csize3, 3), "ms": round(min(t3) * 1e3, 2),
-                                       "kernel_ms": {k: round(v, 3) for k, v in ek3.items() if "enc" in k}, "first_frames_round_trip": ok3,
-                                       "roofline": roofline_of({k: v for k, v in ek3.items() if "enc" in k}, dsize + csize3, min(t3) * 1e3, None, False)}
-                del d_comp3, d_cs3, o3
-            except Exception as ex:                                   # noqa: BLE001  (a leg of the report, not the run)
-                enc_info["level_3"] = {"error": f"{type(ex).__name__}: {ex}"}
     else:
         frames, comp = z_frames, z_comp
         d_comp = torch.from_numpy(np.frombuffer(comp + b"\0" * 64, np.uint8).copy()).to(dev)
@@ -840,7 +871,7 @@ def main():
     d[1:] = np.cumsum([f[1] for f in frames])
     csize = int(c[-1])
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if comp is None:
             comp = bytes(d_comp[:csize].cpu().numpy())             # CPU decodes the very same (GPU-made) archive
         base = cpu_baseline(comp, frames, data, 512 if args.workload == "c3" else 128, level, cks,
@@ -863,17 +894,18 @@ def main():
     torch.cuda.synchronize()                                    # (torch's fills and copies above have landed: the engine's queues are not ordered behind torch's stream)
     for _ in range(args.warmup):
         step()
-    # parity gate before anything is timed: every frame's XXH64 equals the generator's
-    eng.xxh64_frames_dev(d_out, d_d, nframes, d_hash)
-    got = d_hash.cpu().numpy().view(np.uint64)
-    if not np.array_equal(got, np.array(hashes, dtype=np.uint64)) or int(d_st.abs().sum().item()) != 0:
-        raise RuntimeError("GPU decode is not bit-exact against the generator bytes")
-    if not torch.equal(d_out[:dsize], d_src):
-        raise RuntimeError("GPU decode differs from the input bytes")
+    if full:
+        # parity gate before anything is timed: every frame's XXH64 equals the generator's
+        eng.xxh64_frames_dev(d_out, d_d, nframes, d_hash)
+        got = d_hash.cpu().numpy().view(np.uint64)
+        if not np.array_equal(got, np.array(hashes, dtype=np.uint64)) or int(d_st.abs().sum().item()) != 0:
+            raise RuntimeError("GPU decode is not bit-exact against the generator bytes")
+        if not torch.equal(d_out[:dsize], d_src):
+            raise RuntimeError("GPU decode differs from the input bytes")
 
     # Timed region: K steps, two batches in flight (zk_decode_submit_dev / zk_decode_wait: the checksum stage of one
     # batch -- a per-frame serial chain -- overlaps the entropy stages of the next).  Every step is a complete decode
-    # + verification of the whole batch; both output buffers are compared with the input bytes afterwards.
+    # + verification of the whole batch; under --full both output buffers are compared with the input bytes afterwards.
     d_outs = [d_out, torch.empty(dsize + 64, dtype=torch.uint8, device=dev)]
     d_sts = [d_st, torch.zeros(nframes, dtype=torch.int32, device=dev)]
 
@@ -902,30 +934,34 @@ def main():
     run_timed(args.steps)
     torch.cuda.synchronize(); barrier()
     elapsed = time.perf_counter() - t0
-    if not args.sync and (not torch.equal(d_outs[1][:dsize], d_src) or int(d_sts[1].abs().sum().item()) != 0):
-        raise RuntimeError("pipelined GPU decode differs from the input bytes")
-    # the same K steps one batch at a time (zk_decode_frames_dev returns after each batch): reported beside the headline
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    sync_steps = []
-    for _ in range(args.steps):
-        ts_ = time.perf_counter()
-        step()                                                  # (returns when the batch is done: zk_decode_frames_dev synchronises its stream)
-        sync_steps.append(time.perf_counter() - ts_)
-    followed = eng.checksums_followed()                         # frames of the last lone batch whose checksums ran BESIDE the executor
-    torch.cuda.synchronize()
-    sync_elapsed = time.perf_counter() - t1
-    # SURVEY 8d's protocol asks for median and min beside the mean: the headline's K pipelined steps are one span by contract, so two more
-    # spans of K steps are timed the same way (rank-local, behind the contract's span) and every span's ms per step is listed
-    spans = [elapsed]
-    for _ in range(2):
-        torch.cuda.synchronize(); tsp = time.perf_counter()
-        run_timed(args.steps)
-        torch.cuda.synchronize(); spans.append(time.perf_counter() - tsp)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        last = 0 if args.sync else (args.steps - 1) & 1           # the buffers the last timed step wrote
+        dump_outputs(args.dump_outputs, d_outs[last], d_sts[last], dsize, nframes)
+    if full:
+        if not args.sync and (not torch.equal(d_outs[1][:dsize], d_src) or int(d_sts[1].abs().sum().item()) != 0):
+            raise RuntimeError("pipelined GPU decode differs from the input bytes")
+        # the same K steps one batch at a time (zk_decode_frames_dev returns after each batch): reported beside the headline
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        sync_steps = []
+        for _ in range(args.steps):
+            ts_ = time.perf_counter()
+            step()                                                  # (returns when the batch is done: zk_decode_frames_dev synchronises its stream)
+            sync_steps.append(time.perf_counter() - ts_)
+        followed = eng.checksums_followed()                         # frames of the last lone batch whose checksums ran BESIDE the executor
+        torch.cuda.synchronize()
+        sync_elapsed = time.perf_counter() - t1
+        # SURVEY 8d's protocol asks for median and min beside the mean: the headline's K pipelined steps are one span by contract, so two more
+        # spans of K steps are timed the same way (rank-local, behind the contract's span) and every span's ms per step is listed
+        spans = [elapsed]
+        for _ in range(2):
+            torch.cuda.synchronize(); tsp = time.perf_counter()
+            run_timed(args.steps)
+            torch.cuda.synchronize(); spans.append(time.perf_counter() - tsp)
     total_bytes = dsize * world * args.steps
     value = total_bytes / elapsed / 2**30
 
@@ -971,41 +1007,42 @@ def main():
             ref_info["level_3"] = ref_leg(z3[0], z3[1], "the same at level 3, the reference CLI's default: ~60 % more sequences per frame, a 2 MiB window", "reference_made_level_3")
 
     # ---- roofline of the dominant kernel: HIP events on the launch stream, live
-    eng.set_profiling(True)
-    acc = {}
-    nprof = 3
-    for _ in range(nprof):
-        step()
-        for k, ms in eng.kernel_times().items():
-            acc[k] = acc.get(k, 0.0) + ms / nprof
-    eng.set_profiling(False)
-    dom = max(acc, key=acc.get)
-    algo_bytes = csize + dsize                    # decode = c_i + d_i per frame, summed over the launch
-    achieved = algo_bytes / (acc[dom] * 1e-3) / 1e9
-    # HBM bytes actually moved by that kernel: PMC counters cannot be read from inside this process; the
-    # value comes from the committed separate rocprofv3 --pmc passes of this very command (profiles/README.md)
-    traffic, traffic_src = None, None
-    try:
-        with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-            pmc = json.load(f)
-        if pmc.get("workload") == args.workload and nframes == 2048:
-            traffic = pmc["kernels"].get(dom.split("(")[0], {}).get("hbm_bytes")
-            # NOT measured by this run: a constant from the committed counter passes of this command
-            traffic_src = f"profiles/pmc_traffic.json ({pmc.get('collected', 'committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes')}), not this run"
-            if traffic is not None and not _pmc_fresh(pmc, dom.split("(")[0]):
-                traffic, traffic_src = None, "the committed counter pass was taken on other kernel sources (profiles/pmc_traffic.json source_hashes): not quoted"
-    except OSError:
-        pass
+    if full:
+        eng.set_profiling(True)
+        acc = {}
+        nprof = 3
+        for _ in range(nprof):
+            step()
+            for k, ms in eng.kernel_times().items():
+                acc[k] = acc.get(k, 0.0) + ms / nprof
+        eng.set_profiling(False)
+        dom = max(acc, key=acc.get)
+        algo_bytes = csize + dsize                    # decode = c_i + d_i per frame, summed over the launch
+        achieved = algo_bytes / (acc[dom] * 1e-3) / 1e9
+        # HBM bytes actually moved by that kernel: PMC counters cannot be read from inside this process; the
+        # value comes from the committed separate rocprofv3 --pmc passes of this very command (profiles/README.md)
+        traffic, traffic_src = None, None
+        try:
+            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+                pmc = json.load(f)
+            if pmc.get("workload") == args.workload and nframes == 2048:
+                traffic = pmc["kernels"].get(dom.split("(")[0], {}).get("hbm_bytes")
+                # NOT measured by this run: a constant from the committed counter passes of this command
+                traffic_src = f"profiles/pmc_traffic.json ({pmc.get('collected', 'committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes')}), not this run"
+                if traffic is not None and not _pmc_fresh(pmc, dom.split("(")[0]):
+                    traffic, traffic_src = None, "the committed counter pass was taken on other kernel sources (profiles/pmc_traffic.json source_hashes): not quoted"
+        except OSError:
+            pass
 
     # ---- end to end: host buffers in, host buffers out through the zeekstd Encoder / Decoder API (PCIe inside the span)
     e2e_info = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if full and rank == 0 and world == 1 and not args.no_e2e:
         del d_outs, d_sts
         e2e_info = end_to_end(eng, zk, np.asarray(data), nframes, cks)
 
     # ---- configs[0]: the reference's own bench input through the RawEncoder / Encoder / Decoder handles
     c1_info = None
-    if rank == 0 and world == 1 and not args.no_c1:
+    if full and rank == 0 and world == 1 and not args.no_c1:
         c1_info = small_input_leg(eng, zk)
 
     # ---- seek-to-offset latency: BASELINE.json configs[3] as written (a failing leg fails the run)
@@ -1017,7 +1054,7 @@ def main():
     # xGMI).  It runs BEFORE the line is printed and its result (or its error) is part of the line; a watchdog bounds it, so a
     # collective that hangs costs four minutes and an error field, not the line.
     gather_info, gather_failed, gather_hung = None, False, False
-    if world > 1 and use_gpu_archive:
+    if full and world > 1 and use_gpu_archive:
         import threading
         from zeekstd_amd import parallel
         box = {}
@@ -1132,41 +1169,45 @@ def main():
             "metric": "decode_decompressed_GiB_per_s", "value": round(value, 3), "unit": "GiB/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "reference_made_archive": ref_info,
-            "spans_of_K_steps_ms_per_step": {"n": len(spans), "median": round(sorted(spans)[len(spans) // 2] / args.steps * 1e3, 3),
-                                             "min": round(min(spans) / args.steps * 1e3, 3), "mean": round(sum(spans) / len(spans) / args.steps * 1e3, 3),
-                                             "note": "the contract's span first (value / ms_per_step are its), then two more spans of K steps timed alike"},
-            "one_batch_at_a_time": {"value": round(dsize * args.steps / sync_elapsed / 2**30, 3), "unit": "GiB/s",
-                                    "ms_per_step": round(sync_elapsed / args.steps * 1e3, 3), "steps_ms": _stats_ms(sync_steps),
-                                    "checksums_followed": followed,
-                                    "checksums_followed_note": "frames verified by zk_k_xxh64_follow beside the executor (same-XCD hand-off: depends on how the "
-                                                               "dispatcher deals workgroups to XCDs; the rest is verified behind the executor)",
-                                    "note": "same steps through the synchronous zk_decode_frames_dev (rank-local, no overlap between batches)"},
-            "config": {"workload": (f"configs[2]: 4 GiB/GPU, 2048 x 2 MiB frames, level {level}, XXH64 checksums verified"
-                                    if args.workload == "c3" else f"configs[1]: 256 MiB, 128 x 2 MiB frames, level {level}, decode-only"),
-                       "frames_per_gpu": nframes, "frame_size": FRAME, "compressed_bytes_per_gpu": csize,
-                       "batches_in_flight": 1 if args.sync else 2,
-                       "archive": ("GPU encoder of this engine (zk_encode_frames_dev)" if use_gpu_archive else "CPU libzstd (reference Encoder loop)")
-                                  + ", inputs from the SURVEY 8d generator",
-                       "parallelism": f"frames sharded over {world} GPU(s), no data-path collective",
-                       "bit_exact": True, **({"kernel_choice": args.choice} if args.choice else {})},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "step_frac": round(algo_bytes / (sync_elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
-                         "step_frac_note": "the whole step (all kernels, one batch at a time) against the same peak",
-                         "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": {k: round(v, 3) for k, v in acc.items()}},
-            "cpu_baseline": base,
-            "encode": enc_info,
-            "round_trip": ({"value": round(dsize / (enc_info["ms"] * 1e-3 + ms_step * 1e-3) / 2**30, 2), "unit": "GiB/s",
-                            "note": "HBM-resident encode + decode of the same 4 GiB, encode ms + decode ms_per_step (BASELINE metric: encode+decode)"}
-                           if enc_info else None),
-            "end_to_end": e2e_info,
-            "configs0_small_input": c1_info,
-            "rccl_gather": gather_info,
-            "seek": seek_info,
-            "setup_s": round(t_setup, 1),
-        }
+            "vs_baseline": None, "dtype": "u8", "data": "synthetic"}
+        if full:
+            line.update({
+                "reference_made_archive": ref_info,
+                "spans_of_K_steps_ms_per_step": {"n": len(spans), "median": round(sorted(spans)[len(spans) // 2] / args.steps * 1e3, 3),
+                                                 "min": round(min(spans) / args.steps * 1e3, 3), "mean": round(sum(spans) / len(spans) / args.steps * 1e3, 3),
+                                                 "note": "the contract's span first (value / ms_per_step are its), then two more spans of K steps timed alike"},
+                "one_batch_at_a_time": {"value": round(dsize * args.steps / sync_elapsed / 2**30, 3), "unit": "GiB/s",
+                                        "ms_per_step": round(sync_elapsed / args.steps * 1e3, 3), "steps_ms": _stats_ms(sync_steps),
+                                        "checksums_followed": followed,
+                                        "checksums_followed_note": "frames verified by zk_k_xxh64_follow beside the executor (same-XCD hand-off: depends on how the "
+                                                                   "dispatcher deals workgroups to XCDs; the rest is verified behind the executor)",
+                                        "note": "same steps through the synchronous zk_decode_frames_dev (rank-local, no overlap between batches)"}})
+        line["config"] = {"workload": (f"configs[2]: 4 GiB/GPU, 2048 x 2 MiB frames, level {level}, XXH64 checksums verified"
+                                       if args.workload == "c3" else f"configs[1]: 256 MiB, 128 x 2 MiB frames, level {level}, decode-only"),
+                          "frames_per_gpu": nframes, "frame_size": FRAME, "compressed_bytes_per_gpu": csize,
+                          "batches_in_flight": 1 if args.sync else 2,
+                          "archive": ("GPU encoder of this engine (zk_encode_frames_dev)" if use_gpu_archive else "CPU libzstd (reference Encoder loop)")
+                                     + ", inputs from the SURVEY 8d generator",
+                          "parallelism": f"frames sharded over {world} GPU(s), no data-path collective",
+                          "bit_exact": True if full else None,            # checked against the generator's bytes under --full only
+                          **({"kernel_choice": args.choice} if args.choice else {})}
+        if full:
+            line.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                             "step_frac": round(algo_bytes / (sync_elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
+                             "step_frac_note": "the whole step (all kernels, one batch at a time) against the same peak",
+                             "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": {k: round(v, 3) for k, v in acc.items()}},
+                "cpu_baseline": base,
+                "encode": enc_info,
+                "round_trip": ({"value": round(dsize / (enc_info["ms"] * 1e-3 + ms_step * 1e-3) / 2**30, 2), "unit": "GiB/s",
+                                "note": "HBM-resident encode + decode of the same 4 GiB, encode ms + decode ms_per_step (BASELINE metric: encode+decode)"}
+                               if enc_info else None),
+                "end_to_end": e2e_info,
+                "configs0_small_input": c1_info,
+                "rccl_gather": gather_info,
+                "seek": seek_info})
+        line["setup_s"] = round(t_setup, 1)
         if base:
             # The pair that counts for a user of the reference: the archive zeekstd's own CPU Encoder wrote, GPU rate on it over the
             # CPU Decoder's rate on it.  The GPU-made archive (the headline: configs[2] is encode + decode on the GPU) is the slowest
@@ -1187,20 +1228,21 @@ def main():
             if "speedup_vs_cpu_1thread" not in line:           # no reference-made leg in this run (N > 1, --no-ref-archive)
                 line["speedup_vs_cpu_1thread"] = line["speedup_vs_cpu_1thread_gpu_made_archive"]
                 line["speedup_note"] = "GPU and CPU both on the archive this engine's encoder wrote (no reference-made leg in this run)"
-        # the numbers a reader of the line's first 500 characters should find (the driver's tail truncates long lines): short scalars in front
-        def _g(d, *path):
-            for k in path:
-                d = d.get(k) if isinstance(d, dict) else None
-            return d
-        front = {k: line[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
-        front.update({"reference_made_GiB_s": _g(ref_info, "value"), "reference_made_level3_GiB_s": _g(ref_info, "level_3", "value"),
-                      "encode_GiB_s": _g(enc_info, "value"), "encode_level3_GiB_s": _g(enc_info, "level_3", "value"), "encode_level3_ratio": _g(enc_info, "level_3", "ratio"), "round_trip_GiB_s": _g(line.get("round_trip"), "value"),
-                      "seek_p50_us": _g(seek_info, "gpu_made_archive", "gpu_decoder_us", "p50"), "seek_p50_us_reference_made": _g(seek_info, "reference_made_archive", "gpu_decoder_us", "p50"),
-                      "seek_p50_us_cpu_reference": _g(seek_info, "reference_made_archive", "cpu_reference_us", "p50"),
-                      "configs0_decoder_GiB_s": _g(c1_info, "decoder", "value"), "roofline_frac": round(achieved / HBM_PEAK_GBS, 5),
-                      "speedup_vs_cpu_1thread": line.get("speedup_vs_cpu_1thread"), "speedup_vs_cpu_all_cores": line.get("speedup_vs_cpu_all_cores")})
-        front.update({k: v for k, v in line.items() if k not in front})
-        line = front
+        if full:
+            # the numbers a reader of the line's first 500 characters should find (the driver's tail truncates long lines): short scalars in front
+            def _g(d, *path):
+                for k in path:
+                    d = d.get(k) if isinstance(d, dict) else None
+                return d
+            front = {k: line[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
+            front.update({"reference_made_GiB_s": _g(ref_info, "value"), "reference_made_level3_GiB_s": _g(ref_info, "level_3", "value"),
+                          "encode_GiB_s": _g(enc_info, "value"), "encode_level3_GiB_s": _g(enc_info, "level_3", "value"), "encode_level3_ratio": _g(enc_info, "level_3", "ratio"), "round_trip_GiB_s": _g(line.get("round_trip"), "value"),
+                          "seek_p50_us": _g(seek_info, "gpu_made_archive", "gpu_decoder_us", "p50"), "seek_p50_us_reference_made": _g(seek_info, "reference_made_archive", "gpu_decoder_us", "p50"),
+                          "seek_p50_us_cpu_reference": _g(seek_info, "reference_made_archive", "cpu_reference_us", "p50"),
+                          "configs0_decoder_GiB_s": _g(c1_info, "decoder", "value"), "roofline_frac": round(achieved / HBM_PEAK_GBS, 5),
+                          "speedup_vs_cpu_1thread": line.get("speedup_vs_cpu_1thread"), "speedup_vs_cpu_all_cores": line.get("speedup_vs_cpu_all_cores")})
+            front.update({k: v for k, v in line.items() if k not in front})
+            line = front
         print(json.dumps(line), flush=True)
     if shm_comm and not gather_hung:
         shm_lib.zkshm_comm_destroy(shm_comm)

@@ -25,7 +25,7 @@ def test_bench_n_ranks_on_one_gpu(world):
     env = dict(os.environ, HIP_VISIBLE_DEVICES="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--frames", "64", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-seek", "--no-e2e", "--no-c1", "--one-gpu-transport", lib], cwd=ROOT, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", "--no-seek", "--no-e2e", "--no-c1", "--one-gpu-transport", lib], cwd=ROOT, capture_output=True, text=True,
                        timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

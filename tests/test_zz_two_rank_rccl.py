@@ -24,7 +24,7 @@ def test_two_rank_rccl_run_when_two_gpus_are_visible():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--frames", "64", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-seek", "--no-e2e", "--no-c1"], cwd=root, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-seek", "--no-e2e", "--no-c1"], cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["value"] > 0
