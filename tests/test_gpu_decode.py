@@ -11,6 +11,8 @@ from oracle import libzstd_ref as Z
 
 pytestmark = pytest.mark.gpu
 
+XXH64_CHOICES = (0, 1, 2, 3, 5)        # the checksum kernels behind the executor: by batch shape, then each pinned (include/zeekstd_amd.h)
+
 
 def test_engine_reports_gfx950(engine):
     assert "gfx950" in engine.device_name
@@ -52,20 +54,59 @@ def test_xxh64_kernel(engine):
     blob = b"".join(datas)
     off = np.zeros(len(datas) + 1, np.uint64)
     off[1:] = np.cumsum([len(x) for x in datas])
-    h = engine.xxh64_frames(blob, off)
-    assert [int(x) for x in h] == [zko.xxh64(x) for x in datas]
-    assert int(h[-1]) == 0xAD0311EAAD1ED582          # SURVEY 8(d) KAT
+    want = [zko.xxh64(x) for x in datas]
+    try:
+        for k in XXH64_CHOICES:
+            engine.set_kernel_choice(reset=0)
+            engine.set_kernel_choice(xxh64=k)
+            h = engine.xxh64_frames(blob, off)
+            assert [int(x) for x in h] == want, k
+            assert int(h[-1]) == 0xAD0311EAAD1ED582          # SURVEY 8(d) KAT
+    finally:
+        engine.set_kernel_choice(reset=0)
 
 
 def test_xxh64_kernel_on_a_large_batch(engine):
-    """512 frames and more take the sixteen-frames-per-wave kernel (zk_k_xxh64_wide): ragged sizes, frames below one
-    stripe, a last frame shorter than the others, a count that is not a multiple of 16."""
-    for nf, fs, cut in [(768, 65536, 0), (600, 70001, 12345), (513, 31, 0), (520, 100, 7), (1030, 4096 + 9, 4000)]:
-        data = np.frombuffer(zko.gen_random(nf * fs - cut, nf), np.uint8)
-        off = np.arange(nf + 1, dtype=np.uint64) * fs
-        off[-1] -= cut
-        h = engine.xxh64_frames(data.tobytes(), off)
-        assert [int(x) for x in h] == [zko.xxh64(data[int(off[i]):int(off[i + 1])].tobytes()) for i in range(nf)], (nf, fs)
+    """Ragged sizes, frames below one stripe, a last frame shorter than the others, a count that is not a multiple of 16 -- under
+    every kernel zk_xxh64_frames can take: by batch shape (a wave per frame below 1024 frames, four frames per workgroup from
+    there on: zk_k_xxh64_fed<4>), and pinned to zk_k_xxh64 (1), zk_k_xxh64_wide (2), zk_k_xxh64_lean (3), zk_k_xxh64_fed<4> (5)."""
+    try:
+        for nf, fs, cut in [(768, 65536, 0), (600, 70001, 12345), (513, 31, 0), (520, 100, 7), (1030, 4096 + 9, 4000)]:
+            data = np.frombuffer(zko.gen_random(nf * fs - cut, nf), np.uint8)
+            off = np.arange(nf + 1, dtype=np.uint64) * fs
+            off[-1] -= cut
+            want = [zko.xxh64(data[int(off[i]):int(off[i + 1])].tobytes()) for i in range(nf)]
+            for k in XXH64_CHOICES:
+                engine.set_kernel_choice(reset=0)
+                engine.set_kernel_choice(xxh64=k)
+                h = engine.xxh64_frames(data.tobytes(), off)
+                assert [int(x) for x in h] == want, (nf, fs, k)
+    finally:
+        engine.set_kernel_choice(reset=0)
+
+
+def test_xxh64_frames_dev_hashes_the_ranges_it_is_given(engine):
+    """zk_xxh64_frames_dev hashes data[off[i], off[i+1]) also when off[0] is not 0 (the kernels address a frame from off[0] on;
+    a table that began elsewhere once hashed the bytes off[0] too early), under every kernel."""
+    import torch
+    dev = torch.device("cuda", 0)
+    data = np.frombuffer(zko.gen_random(3 << 20, 0x0FF0), np.uint8)
+    d_data = torch.from_numpy(data.copy()).to(dev)
+    lens = [0, 1, 31, 32, 33, 1023, 1024, 1025, 65536 + 3, 5] * 4
+    try:
+        for start in (1, 4097, (2 << 20) + 13):
+            off = np.zeros(len(lens) + 1, np.uint64); off[1:] = np.cumsum(lens); off += np.uint64(start)
+            want = [zko.xxh64(data[int(off[i]):int(off[i + 1])].tobytes()) for i in range(len(lens))]
+            d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+            d_h = torch.zeros(len(lens), dtype=torch.int64, device=dev)
+            for k in XXH64_CHOICES:
+                engine.set_kernel_choice(reset=0)
+                engine.set_kernel_choice(xxh64=k)
+                d_h.fill_(0)
+                engine.xxh64_frames_dev(d_data, d_off, len(lens), d_h)
+                assert [int(x) for x in d_h.cpu().numpy().view(np.uint64)] == want, (start, k)
+    finally:
+        engine.set_kernel_choice(reset=0)
 
 
 def test_checksum_mismatch_is_reported(engine):

@@ -32,6 +32,8 @@ VARIANTS = {
     "exec512_wide_checksums": dict(exec_lanes=512, xxh64=2, small_path=1),
     # (r6) the chains' wave fed by producer waves: four frames per workgroup (what large batches take)
     "exec256_checksums_fed4": dict(exec_lanes=256, xxh64=5, small_path=1),
+    # sixteen frames per wave in 64 registers (zk_k_xxh64_lean): nothing takes it by shape
+    "predef_exec256_checksums_lean": dict(fse_shared=1, exec_lanes=256, xxh64=3, small_path=1),
 }
 
 

@@ -516,7 +516,13 @@ extern "C" int zk_xxh64_frames_dev(zk_engine *e, const void *d_data, const void 
     if (count == 0) return 0;
     ZK_HIP(hipSetDevice(e->device));
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    zk_launch_xxh64(st, (const uint8_t *)d_data, (const uint64_t *)d_off, 0, count, nullptr, (uint64_t *)d_out, e->choice);
+    // the kernels address frame i at data + (off[i] - off[0]) (the decoder hands them its output, which begins with the batch's first
+    // frame); this entry point hashes data[off[i], off[i+1]) as documented, so they get the data pointer moved by off[0]
+    // (found by tests/test_gpu_past_4gib.py: a table that did not start at 0 hashed the wrong bytes)
+    uint64_t off0 = 0;
+    ZK_HIP(hipMemcpyAsync(&off0, d_off, 8, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    zk_launch_xxh64(st, (const uint8_t *)d_data + off0, (const uint64_t *)d_off, 0, count, nullptr, (uint64_t *)d_out, e->choice);
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
     return 0;
