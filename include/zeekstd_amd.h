@@ -104,12 +104,18 @@ enum {
     ZK_CHOICE_EXEC_SEG = 10,      /* the executor in segments, several workgroups per frame (zk_k_seg_prep / zk_k_exec_seg / zk_k_exec_fill): 1 never, 2 always
                                      (decodes without a prefix); 0 = by batch shape */
     ZK_CHOICE_SEG_KIB = 11,       /* ... output KiB per segment (1..128; 0 = 128) */
-    ZK_CHOICE_SEG_FILL = 12       /* ... its fill pass: 1 zk_k_exec_fill<1024> (rounds through memory), 2 zk_k_exec_fill<256>, 3 zk_k_exec_fill_lds (holes in LDS); 0 by batch size */
+    ZK_CHOICE_SEG_FILL = 12,      /* ... its fill pass: 1 zk_k_exec_fill<1024> (rounds through memory), 2 zk_k_exec_fill<256>, 3 zk_k_exec_fill_lds (holes in LDS); 0 by batch size */
+    ZK_CHOICE_ENTROPY = 13        /* literals and sequences of a device-pointer batch: 1 = zk_k_huf beside the sequence kernels on two queues, 2 = one kernel
+                                   * (zk_k_entropy_frame) for every batch that qualifies -- no frame with more than one set of own tables -- whatever its
+                                   * size; 0 = by batch shape.  zk_engine_entropy_fused says which one ran */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
  * verified by zk_k_xxh64_follow, beside the executor; the others were verified behind it.  A diagnostic: results do not depend on it. */
 uint64_t zk_engine_checksums_followed(const zk_engine *e);
+/* 1 if the last finished device-pointer decode ran literals and sequences in one kernel (zk_k_entropy_frame), 0 if as two kernels side by
+ * side.  A diagnostic: results do not depend on it. */
+int zk_engine_entropy_fused(const zk_engine *e);
 int zk_engine_kernel_count(void);
 const char *zk_engine_kernel_name(int k);
 int zk_engine_kernel_times(const zk_engine *e, float *ms_out, int n);

@@ -9,6 +9,8 @@
 //   zk_k_walk (fill)   one lane per frame -> ZkBlock[] (block list, table inheritance)
 //   zk_k_huf           wave 0: one lane per Huffman stream (4 per block), tables in an LDS pool sized by tree depth;
 //                      wave 1: companion lanes (touch the stream ahead, store the decoded packs) -> literal scratch
+//   zk_k_entropy_frame large batches of this engine's own frames: zk_k_fse_predef_fed's two waves and zk_k_huf's two in ONE workgroup per
+//                      64 blocks, instead of the two kernels on two queues
 //   zk_k_fse_predef    blocks with predefined tables: one lane per block, 64 blocks per wave in lock step, shared
 //                      tables, cooperative 64-B record stores -> ZkSeq[] (+ out_size, symbolic reps)
 //   zk_k_fse_quad      blocks with their own tables: FSE tables in LDS, a quad of lanes per block (one lane per state
@@ -128,8 +130,10 @@ __global__ __launch_bounds__(1024) void zk_k_scan(const ZkFrameInfo *infos, uint
 // ------------------------------------------------------------------------------------------------ Huffman literals
 // 64 lanes = 16 blocks x 4 streams.  The decode tables live in a 16 KiB LDS pool that is carved up by each tree's
 // depth (2^maxbits u16 cells): sixteen 9-bit tables fit at once, deeper trees take the blocks in several passes.
-// A workgroup therefore needs ~21 KiB of LDS and 7 of them share a CU; the chain per symbol
-// (shift -> LDS cell -> shift) is latency bound, so lanes in flight per CU is what sets the speed.
+// A workgroup therefore needs 25 800 bytes of LDS (code object) and SIX of them share a CU: 1 536 of a 4 GiB batch's 8 192 workgroups
+// at a time.  The chain per symbol is shift -> LDS cell -> shift; more decoders per CU do not buy much (a pool of 4 096 / 2 560 cells,
+// 9 / 11 workgroups per CU: 2.82 -> 2.63 / 2.69 ms, profiles/r06f_huf_pool_probe.txt).  Beside zk_k_fse_predef_fed, whose 2 048
+// workgroups fill every CU's LDS in one round, this kernel waits for them to end: zk_k_entropy_frame below.
 constexpr int ZK_HUF_BLOCKS = 16;
 constexpr uint32_t ZK_HUF_POOL = 8192;           // u16 cells
 constexpr int32_t ZK_HUF_AHEAD = 192;            // bytes the companion wave stays ahead of a stream's read position
@@ -190,10 +194,29 @@ __device__ void zk_huf_companion(const uint8_t *base, uint32_t len, uint8_t *dst
     asm volatile("" :: "v"(sink));
 }
 
-// The body of the kernel for block group `group` (16 blocks); also called in a loop by zk_k_small_entropy.
-__device__ __forceinline__ void zk_huf_group(uint32_t group, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint8_t *lit_scratch)
+// A barrier of TWO waves of a workgroup (the Huffman half of zk_k_entropy_frame: its decoder and its companion), over an LDS word
+// that only counts up: s_barrier would hold the workgroup's other waves -- the sequence walker -- at every Huffman pass.  Both waves
+// are resident, so the spin ends; `gen` is each thread's count of arrivals so far (both waves call it the same number of times).
+struct ZkPairBar { uint32_t n; };
+__device__ __forceinline__ void zk_pair_sync(ZkPairBar *bar, uint32_t &gen, uint32_t lane)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t pool[ZK_HUF_POOL];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");           // what this wave wrote is visible before it arrives
+    gen += 2;
+    if (lane == 0) atomicAdd(&bar->n, 1u);
+    while (zk_lds_ld<uint32_t>(&bar->n) < gen) __builtin_amdgcn_s_sleep(1);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// The body of the kernel for block group `group` (16 blocks); also called in a loop by zk_k_small_entropy.
+// POOL: cells of the table pool.  PAIR: the caller's workgroup has other waves at other work (zk_k_entropy_frame) -- tid counts from the
+// decoder wave's first lane and the barriers are zk_pair_sync's.
+template <uint32_t POOL = ZK_HUF_POOL, bool PAIR = false>
+__device__ __forceinline__ void zk_huf_group(uint32_t group, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint8_t *lit_scratch,
+                                             uint32_t tid = threadIdx.x, ZkPairBar *bar = nullptr, uint32_t *gen = nullptr)
+{
+    static_assert(POOL >= 2048 && ZK_HUF_BLOCKS * sizeof(ZkHufTmp) <= POOL * sizeof(uint16_t), "a maximum-depth table and the parse scratch fit the pool");
+    auto sync = [&]() { if constexpr (PAIR) zk_pair_sync(bar, *gen, tid & 63); else __syncthreads(); };
+    __shared__ __attribute__((aligned(16))) uint16_t pool[POOL];
     __shared__ ZkHufHdr hdr[ZK_HUF_BLOCKS];
     __shared__ uint32_t s_maxbits[ZK_HUF_BLOCKS], s_desc[ZK_HUF_BLOCKS], s_n[ZK_HUF_BLOCKS];
     __shared__ ZkHufMail mail;
@@ -201,8 +224,8 @@ __device__ __forceinline__ void zk_huf_group(uint32_t group, const uint8_t *comp
     // wave 0 decodes (lane = block slot x 4 streams), wave 1 mirrors it lane for lane and touches cache lines ahead.
     // A workgroup with fewer than 4 blocks left keeps >= 16 lanes active: the extra lanes shadow valid streams
     // (< 16 active lanes run ~3x slower on gfx950, tools/ubench/lat3.hip); shadows never store to HBM
-    const uint32_t t = threadIdx.x & 63;
-    const bool decoder = threadIdx.x < 64, companion = threadIdx.x >= 64 && threadIdx.x < 128;     // (further waves of a caller's workgroup only pass the barriers)
+    const uint32_t t = tid & 63;
+    const bool decoder = tid < 64, companion = tid >= 64 && tid < 128;     // (further waves of a caller's workgroup only pass the barriers)
     const uint32_t wb = group * ZK_HUF_BLOCKS;
     const uint32_t nvalid = nblocks - wb < (uint32_t)ZK_HUF_BLOCKS ? nblocks - wb : (uint32_t)ZK_HUF_BLOCKS;
     const bool real = t < 4 * nvalid;
@@ -224,14 +247,14 @@ __device__ __forceinline__ void zk_huf_group(uint32_t group, const uint8_t *comp
         }
         s_desc[slot] = r; s_maxbits[slot] = mb; s_n[slot] = n;
     }
-    __syncthreads();
+    sync();
     // pool layout: blocks in slot order, a new pass whenever the next table does not fit
     uint32_t my_pass = 0, my_at = 0, npass;
     {
         uint32_t pass = 0, acc = 0;
         for (uint32_t j = 0; j < (uint32_t)ZK_HUF_BLOCKS; j++) {
             const uint32_t sz = s_desc[j] ? 1u << s_maxbits[j] : 0u;
-            if (acc + sz > ZK_HUF_POOL) { pass++; acc = 0; }
+            if (acc + sz > POOL) { pass++; acc = 0; }
             if (j == slot) { my_pass = pass; my_at = acc; }
             acc += sz;
         }
@@ -272,15 +295,15 @@ __device__ __forceinline__ void zk_huf_group(uint32_t group, const uint8_t *comp
             }
         }
         if (decoder) { mail.state[t] = zk_huf_mail_state(0, (int32_t)slen - 40); mail.consumed[t] = 0; }
-        if (threadIdx.x == 0) s_done = 0;
-        __syncthreads();
+        if (tid == 0) s_done = 0;
+        sync();
         if (decoder) {
             if (have) ok = zk_huf_decode_stream(tab, mb, sbase, slen, sdst, sn, real, &mail, t);
             zk_lds_st<uint32_t>(&s_done, 1u);
         } else if (companion && have && real) {
             zk_huf_companion(sbase, slen, sdst + ((0 - (uintptr_t)sdst) & 7), &mail, t, &s_done);     // packs start at the 8-byte aligned output position
         }
-        __syncthreads();
+        sync();
     }
     if (decoder && active && !ok && real) blocks[bi].status = ZK_E_CORRUPTION;
 }
@@ -680,6 +703,94 @@ __global__ __launch_bounds__(2 * ZK_FSEP_LANES) void zk_k_fse_predef_fed(const u
         o->pad = 1;
     } else if (active && bs_off < b.bsize) {
         // feeder: aligned words of the lane's bitstream, last word first (ZkRevL::word_count / W(j))
+        const uint8_t *base = comp + b.src + bs_off;
+        const uint32_t len = b.bsize - bs_off, nwords = ZkRevL::word_count(base, len);
+        const uint8_t *ptr = reinterpret_cast<const uint8_t *>((((uintptr_t)base + len) + 7) & ~(uintptr_t)7) - 8;
+        uint32_t f = 0;
+        while (f < nwords && !zk_lds_ld<uint32_t>(&s_done)) {
+            if (f - zk_lds_ld<uint32_t>(&feed.taken[lane]) < ZK_REVL_RING) {
+                const uint64_t w = *reinterpret_cast<const uint64_t *>(ptr);
+                zk_lds_st<uint64_t>(&feed.ring[f % ZK_REVL_RING][lane], w);
+                f++; ptr -= 8;
+                zk_lds_st<uint32_t>(&feed.filled[lane], f);
+            } else __builtin_amdgcn_s_sleep(1);
+        }
+    }
+}
+
+// Literals AND sequences of 64 consecutive blocks (a 2 MiB frame of this encoder's 32 KiB blocks) in one workgroup of four waves:
+// waves 0 / 1 are zk_k_fse_predef_fed's walker and feeder, waves 2 / 3 zk_k_huf's decoder and companion, which take the 64 blocks'
+// literals as four groups of 16, one after another.  The lane code is the two kernels'; what changes is who shares a CU: launched as
+// two kernels, zk_k_fse_predef_fed's 2 048 workgroups fill every CU's LDS (8 x 20 384 B of 160 KiB) and zk_k_huf starts when they end
+// (one batch at a time: 3.1 and 2.8 ms alone, 5.4 ms as a pair; profiles/r07_entropy_span_parent.txt).  Here every workgroup brings
+// its own Huffman half: 5.2 ms one batch at a time, the step with two batches in flight 12.43-12.48 against 12.70-12.73 ms
+// (profiles/r07_entropy_fused.txt).  The two halves meet at the two barriers in front of their loops and never again: the Huffman half synchronises its
+// two waves through an LDS word (zk_pair_sync), the walker and its feeder through their mailboxes as before.
+// Budget (code object, gfx950): 37 992 bytes of LDS -- the walker's tables, rings and feed 20 384 as in zk_k_fse_predef_fed, the
+// Huffman half 17.6 KiB with a pool of 4 096 cells -- and 86 registers: FOUR workgroups per CU, 16 waves, two rounds for 2 048 frames.
+// Eight per CU (every frame resident at once, what would let the stage end with its longer half) need <= 20 480 bytes per workgroup,
+// and the walker's half alone takes 20 384: not without smaller tables for the walk.  A workgroup of 128 blocks carries two frames' table
+// sets and twice the rings: the same bytes per block.
+constexpr uint32_t ZK_ENT_POOL = 4096;
+__global__ __launch_bounds__(4 * ZK_FSEP_LANES) void zk_k_entropy_frame(const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, ZkSeqP *seqs, uint8_t *lit_scratch)
+{
+    __shared__ ZkSeqTablesT<ZkCells64> T;
+    __shared__ __attribute__((aligned(16))) ZkSeqP ring[ZK_FSEP_LANES][ZK_FSEP_RING];
+    __shared__ ZkCoopFlush coop;
+    __shared__ ZkRevLShared feed;
+    __shared__ ZkFseShare share;
+    __shared__ uint32_t llv[36], mlv[53], s_done;
+    __shared__ ZkPairBar bar;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const bool walker = tid < 64, fse_half = tid < 128;
+    {
+        const uint32_t ll_init[36] = ZK_LL_TABLE;
+        const uint32_t ml_init[53] = ZK_ML_TABLE;
+        if (tid < 36) llv[tid] = ll_init[tid];
+        if (tid < 53) mlv[tid] = ml_init[tid];
+        if (walker) { feed.filled[lane] = 0; feed.taken[lane] = 0; }
+        if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; s_done = 0; share.ok = 0; bar.n = 0; }
+    }
+    __syncthreads();
+    const uint32_t bi = blockIdx.x * ZK_FSEP_LANES + lane;
+    ZkBlock b;
+    ZkFsePick pk;
+    pk.go = false; pk.match = false;
+    if (fse_half) {
+        if (bi < nblocks) b = blocks[bi];
+        pk = zk_fse_share_pick(nblocks, bi, b);                       // both waves, same verdict
+        if (pk.go) {
+            if (tid < 16) zk_fse_share_build<ZkCells64>(comp, blocks, pk, &T, &share, llv, mlv);
+            if (walker) {
+                coop.base[lane] = pk.match ? b.seq_base : 0;
+                coop.nseq[lane] = pk.match ? b.nseq : 0;
+                if (pk.match) atomicMax(&coop.nloop, b.nseq);
+            }
+        }
+    }
+    __syncthreads();                                                  // the last barrier of the whole workgroup
+    if (!fse_half) {
+        uint32_t gen = 0;
+        for (uint32_t g = 4 * blockIdx.x; g < 4 * blockIdx.x + 4 && g * ZK_HUF_BLOCKS < nblocks; g++) {
+            zk_huf_group<ZK_ENT_POOL, true>(g, comp, blocks, nblocks, lit_scratch, tid - 2 * ZK_FSEP_LANES, &bar, &gen);
+            zk_pair_sync(&bar, gen, lane);                           // the group's LDS state is re-initialised by the next one
+        }
+        return;
+    }
+    if (!pk.go || !share.ok) return;                                  // blocks left with pad == 0: the pass behind this kernel takes them
+    const bool active = pk.match;
+    const uint32_t bs_off = active ? zk_fse_share_offset(pk, bi, b, &share) : 0;
+    if (walker) {
+        zk_seq_walk<ZK_FSEP_RING, ZkRevL, ZkCells64>(comp, b, bs_off, T.ll, T.of, T.ml, share.al, ring[lane], seqs, llv, mlv, true, &coop, active, lane, &feed);
+        zk_lds_st<uint32_t>(&s_done, 1u);
+        if (!active) return;
+        ZkBlock *o = &blocks[bi];
+        o->out_size = b.out_size;
+        o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
+        if (b.status != ZK_OK) o->status = b.status;      // (never OK over the Huffman half's verdict: the two run side by side)
+        o->pad = 1;
+    } else if (active && bs_off < b.bsize) {
+        // feeder: as in zk_k_fse_predef_fed
         const uint8_t *base = comp + b.src + bs_off;
         const uint32_t len = b.bsize - bs_off, nwords = ZkRevL::word_count(base, len);
         const uint8_t *ptr = reinterpret_cast<const uint8_t *>((((uintptr_t)base + len) + 7) & ~(uintptr_t)7) - 8;
@@ -2543,6 +2654,28 @@ void zk_launch_huf(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_
     if (!nblocks) return;
     hipLaunchKernelGGL(zk_k_huf, dim3((nblocks + ZK_HUF_BLOCKS - 1) / ZK_HUF_BLOCKS), dim3(128), 0, st, comp, blocks, nblocks, lit);
 }
+static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k);
+// which shared-table kernel a batch gets (zk_launch_fse); 0: none, the batch is small and every block takes a quad of lanes
+static int zk_fse_shared_kernel(uint32_t nblocks, const ZkKernelChoice &k, uint32_t frames)
+{
+    const uint32_t wgs = (nblocks + ZK_FSEP_LANES - 1) / ZK_FSEP_LANES;
+    if (k.fse_own == 0 && k.fse_shared == 0 && nblocks <= 16u * 256u) return 0;
+    return k.fse_shared ? k.fse_shared : (frames && (uint64_t)nblocks < 64ull * frames) ? 3 : wgs >= 6 * 256 ? 2 : 1;
+}
+// Literals and sequences in ONE kernel (zk_k_entropy_frame) where zk_launch_fse would run zk_k_fse_predef_fed over a batch whose frames
+// each define at most one set of tables (this engine's encoder); k.entropy == 2 asks for it whatever the batch's size.  false: not
+// launched, the caller runs zk_launch_huf || zk_launch_fse.
+bool zk_entropy_fused_wanted(uint32_t nblocks, uint32_t n_own_tables, const ZkKernelChoice &k, uint32_t frames)
+{
+    if (!nblocks || k.entropy == 1 || k.fse_own || n_own_tables > frames) return false;
+    if (k.entropy == 2) return k.fse_shared == 0 || k.fse_shared == 2;
+    return ZK_ENTROPY_FUSED_DEFAULT && zk_fse_shared_kernel(nblocks, k, frames) == 2;
+}
+void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, uint8_t *lit, const ZkKernelChoice &k)
+{
+    hipLaunchKernelGGL(zk_k_entropy_frame, dim3((nblocks + ZK_FSEP_LANES - 1) / ZK_FSEP_LANES), dim3(4 * ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs, lit);
+    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k);
+}
 void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, uint32_t frames)
 {
     if (!nblocks) return;
@@ -2562,10 +2695,16 @@ void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_
     }
     // blocks that share their tables with their neighbours (predefined, or one set per frame): one lane each
     // frames of fewer than 64 blocks: a workgroup's 64 blocks span several frames = several table sets
-    const int shared = k.fse_shared ? k.fse_shared : (frames && (uint64_t)nblocks < 64ull * frames) ? 3 : wgs >= 6 * 256 ? 2 : 1;
+    const int shared = zk_fse_shared_kernel(nblocks, k, frames);
     if (shared == 3) hipLaunchKernelGGL(zk_k_fse_sets, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
     else if (shared == 2) hipLaunchKernelGGL(zk_k_fse_predef_fed, dim3(wgs), dim3(2 * ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
     else hipLaunchKernelGGL(zk_k_fse_predef<ZkRevU>, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
+    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k);
+}
+// The pass behind the shared-table kernel (zk_launch_fse, zk_launch_entropy): the blocks it has not marked done.
+static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k)
+{
+    const int own_kernel = k.fse_own;
     // blocks with their own tables (every block is visited, the others return at once): a quad of lanes per block.
     // While everything fits in one round, small workgroups (16 blocks, one walking wave + the toucher: 45 KiB of LDS,
     // three per CU) spread the blocks over the CUs and a block's chain latency is all that counts (measured, 2048

@@ -32,6 +32,7 @@ struct zk_engine {
         zk_devbuf seg_tab, seg_cnt, seg_holes, seg_tiles;            // the executor in segments: ZkSeg records, per-frame / per-segment counts, hole records, tile counts
         uint64_t *h_words = nullptr;
         bool ready = false;
+        bool fused = false;          // the batch enqueued last took zk_k_entropy_frame
     } dctx[ZK_MAX_CTX];
     bool slot_busy[2] = {false, false};
     int next_slot = 0;
@@ -49,6 +50,7 @@ struct zk_engine {
     bool profiling = false;
     ZkKernelChoice choice;           // zk_engine_set_kernel_choice: all zero = by batch shape
     uint64_t followed = 0;           // frames of the last finished decode whose checksums zk_k_xxh64_follow verified (zk_engine_checksums_followed)
+    bool entropy_fused = false;      // the last finished decode ran zk_k_entropy_frame, not zk_k_huf || the sequence kernels (zk_engine_entropy_fused)
     int pipe_contexts = 0;           // host pipeline: decode contexts in flight (0 = default) and chunk size, zk_hostpipe_tune
     uint64_t pipe_chunk_bytes = 0;
     hipEvent_t ev_start[ZK_NKERNELS] = {}, ev_stop[ZK_NKERNELS] = {};

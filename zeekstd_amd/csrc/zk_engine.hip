@@ -68,6 +68,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     case ZK_CHOICE_SMALL_PATH: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; k.small_path = value; return 0;
     case ZK_CHOICE_EXEC_SEG: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; k.exec_seg = value; return 0;
     case ZK_CHOICE_SEG_KIB: if (value < 0 || value > 128) return ZK_ERR_ARGUMENT; k.seg_kib = value; return 0;
+    case ZK_CHOICE_ENTROPY: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; k.entropy = value; return 0;
     case ZK_CHOICE_SEG_FILL: if (value < 0 || value > 3) return ZK_ERR_ARGUMENT; k.seg_fill = value; return 0;
     case ZK_CHOICE_PIPE_CONTEXTS: if (value < 0 || value > ZK_MAX_CTX) return ZK_ERR_ARGUMENT; e->pipe_contexts = value; zk_hostpipe_tune(e); return 0;
     case ZK_CHOICE_PIPE_CHUNK_MIB: if (value < 0 || value > 4096) return ZK_ERR_ARGUMENT; e->pipe_chunk_bytes = (uint64_t)value << 20; zk_hostpipe_tune(e); return 0;
@@ -76,6 +77,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
 }
 extern "C" int zk_engine_set_fse_kernel(zk_engine *e, int mode) { return zk_engine_set_kernel_choice(e, ZK_CHOICE_FSE_OWN, mode); }
 extern "C" uint64_t zk_engine_checksums_followed(const zk_engine *e) { return e ? e->followed : 0; }
+extern "C" int zk_engine_entropy_fused(const zk_engine *e) { return e && e->entropy_fused ? 1 : 0; }
 extern "C" int zk_engine_kernel_count(void) { return ZK_NKERNELS; }
 extern "C" const char *zk_engine_kernel_name(int k)
 {
@@ -319,7 +321,12 @@ int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a)
     { zk_kernel_timer t(e, ZK_K_WALK_FILL, st); zk_launch_walk(st, comp, a.comp_size, c_off, d_off, first, count, a.ids, a.out_off, a.dst_cap, bases, blocks, infos); }
     // literals (huf) and sequences (fse) of a block are independent: the two kernels run side by side on two queues;
     // with per-kernel timing on they are serialised instead
-    if (e->profiling || a.single_queue) {
+    // ... or, where the sequences would get zk_k_fse_predef_fed, both in one kernel whose workgroups each bring a Huffman half and a
+    // sequence half (zk_k_entropy_frame: no second queue, no events)
+    const bool fused = !e->profiling && !a.single_queue && zk_entropy_fused_wanted((uint32_t)nblocks, n_own, e->choice, count);
+    e->dctx[c.slot].fused = fused;
+    if (fused) zk_launch_entropy(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, lit, e->choice);
+    else if (e->profiling || a.single_queue) {
         { zk_kernel_timer t(e, ZK_K_HUF, st); zk_launch_huf(st, comp, blocks, (uint32_t)nblocks, lit); }
         { zk_kernel_timer t(e, ZK_K_FSE, st); zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count); }
     } else {
@@ -360,6 +367,7 @@ int zk_decode_finish(zk_engine *e, zk_dec_ctx &c)
     ZK_HIP(hipStreamSynchronize(c.st));
     ZK_HIP(hipGetLastError());
     zk_profile_collect(e);
+    e->entropy_fused = e->dctx[c.slot].fused;
     e->followed = c.h_words[6] & 0xFFFFFFFFull;          // (the high half counts frames the checksum waves hashed and found different)
     if (c.h_words[3] != ~0ull) return -(int)(uint32_t)(c.h_words[3] & 0xFFFFFFFFu);
     return 0;

@@ -55,7 +55,8 @@ class Engine:
             self._raise(rc)
 
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
-               "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12}
+               "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
+               "entropy": 13}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -73,6 +74,10 @@ class Engine:
     def checksums_followed(self):
         """Frames of the last finished decode that zk_k_xxh64_follow verified beside the executor (zk_engine_checksums_followed)."""
         return int(lib.zk_engine_checksums_followed(self._h))
+
+    def entropy_fused(self):
+        """Whether the last finished decode ran literals and sequences in one kernel, zk_k_entropy_frame (zk_engine_entropy_fused)."""
+        return bool(lib.zk_engine_entropy_fused(self._h))
 
     def set_kernel_choice(self, **kw):
         """Pins kernel variants (zk_engine_set_kernel_choice): e.g. set_kernel_choice(fse_shared=2, exec_lanes=256, xxh64=2) runs the
