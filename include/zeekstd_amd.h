@@ -105,9 +105,10 @@ enum {
                                      (decodes without a prefix); 0 = by batch shape */
     ZK_CHOICE_SEG_KIB = 11,       /* ... output KiB per segment (1..128; 0 = 128) */
     ZK_CHOICE_SEG_FILL = 12,      /* ... its fill pass: 1 zk_k_exec_fill<1024> (rounds through memory), 2 zk_k_exec_fill<256>, 3 zk_k_exec_fill_lds (holes in LDS); 0 by batch size */
-    ZK_CHOICE_ENTROPY = 13        /* literals and sequences of a device-pointer batch: 1 = zk_k_huf beside the sequence kernels on two queues, 2 = one kernel
+    ZK_CHOICE_ENTROPY = 13,       /* literals and sequences of a device-pointer batch: 1 = zk_k_huf beside the sequence kernels on two queues, 2 = one kernel
                                    * (zk_k_entropy_frame) for every batch that qualifies -- no frame with more than one set of own tables -- whatever its
                                    * size; 0 = by batch shape.  zk_engine_entropy_fused says which one ran */
+    ZK_CHOICE_RANGE_PASS_MIB = 14 /* zk_read_ranges*: decoded MiB of scratch per pass (1..2^20; 0 = 1024).  A pass is never less than one frame */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -146,6 +147,37 @@ int zk_decode_frames_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, c
  * seek at a time, lib/src/decode.rs:402-437): decode archive frames d_ids[0..count) (uint32, any order, repeats allowed) of a
  * device-resident archive; frame d_ids[i] lands at d_dst + d_out_off[i], d_out_off being the count + 1 prefix sums of the
  * selected frames' decompressed sizes (uint64).  d_c_off / d_d_off are the archive's full n+1 prefix arrays. */
+int zk_decode_frame_list_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off,
+                             const void *d_ids, const void *d_out_off, uint32_t count, void *d_dst, uint64_t dst_cap,
+                             int verify, void *d_frame_status, void *stream);
+
+/* Batched reads (the bulk form of set_offset / set_offset_limit / read, lib/src/decode.rs:402-437, which serves one seek at a time):
+ * range i is bytes [d_offs[i], d_offs[i] + d_lens[i]) of the DECOMPRESSED stream (uint64 arrays of count entries) and lands at
+ * d_dst + d_dst_off[i]; d_dst_off == NULL packs the ranges back to back in list order (prefix sums of the lengths, made on the
+ * device; a range outside the stream takes no room).  d_c_off / d_d_off are the archive's full n_frames + 1 prefix arrays.  Ranges
+ * may come in any order, overlap, repeat, be empty, cross any number of frames and exceed 4 GiB.  An offset on a frame boundary
+ * belongs to the frame that starts there and empty frames are skipped (seek_table.rs:579-596).
+ *   - exactly the bytes of the ranges are written: what lies between or behind the destinations stays untouched (destinations may
+ *     be padded and aligned at will).  Destinations that overlap each other are the caller's error and are not detected.
+ *   - every frame some range touches is decoded once, into scratch of the engine, whatever number of ranges touch it; the others,
+ *     and frames of decompressed size 0, are not decoded.  The scratch holds at most ZK_CHOICE_RANGE_PASS_MIB of decoded frames (1 GiB
+ *     by default, one frame at least): a call that touches more runs in passes.  zk_engine_ranges_frames_decoded counts the frames.
+ *   - verify != 0: the Content_Checksum of every touched frame that carries one is verified, over the whole frame.
+ *   - d_range_status (optional, int32, count entries): 0; ZK_ERR_OFFSET_OUT_OF_RANGE for a range that leaves the stream, -70
+ *     (dstSize_tooSmall) for one whose destination leaves dst_cap -- such a range writes nothing, the others are served --; or
+ *     -(ZSTD_ErrorCode) of the first frame it touches that failed to decode or verify -- its bytes are then unspecified within its own
+ *     destination, ranges that touch good frames only are delivered all the same.
+ * Returns 0, or the status of the first failing range in list order; engine errors as everywhere.  There is no prefix mode.
+ * zk_read_ranges: host pointers; only the compressed bytes of touched frames are uploaded. */
+int zk_read_ranges_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off, uint32_t n_frames,
+                       const void *d_offs, const void *d_lens, const void *d_dst_off, uint32_t count,
+                       void *d_dst, uint64_t dst_cap, int verify, void *d_range_status, void *stream);
+int zk_read_ranges(zk_engine *e, const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off, const uint64_t *d_off, uint32_t n_frames,
+                   const uint64_t *offs, const uint64_t *lens, const uint64_t *dst_off, uint32_t count,
+                   uint8_t *dst, uint64_t dst_cap, int verify, int32_t *range_status);
+/* Frames the last zk_read_ranges* call decoded (every touched frame once).  A diagnostic. */
+uint64_t zk_engine_ranges_frames_decoded(const zk_engine *e);
+
 /* Decode with a raw-content prefix (patch mode): what the reference does with ZSTD_DCtx_refPrefix before the first
  * frame and again after every frame end (lib/src/decode.rs:212-214, 248-255) -- every frame of the batch sees the
  * same prefix right before its first byte and a match may start up to prefix_len bytes before the frame.  With a
@@ -157,10 +189,6 @@ int zk_decode_frames_prefix_dev(zk_engine *e, const void *d_comp, uint64_t comp_
 int zk_decode_frames_prefix(zk_engine *e, const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off,
                             const uint64_t *d_off, uint32_t first, uint32_t count, const uint8_t *prefix, uint64_t prefix_len,
                             uint8_t *dst, uint64_t dst_cap, int verify, int32_t *frame_status);
-
-int zk_decode_frame_list_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off,
-                             const void *d_ids, const void *d_out_off, uint32_t count, void *d_dst, uint64_t dst_cap,
-                             int verify, void *d_frame_status, void *stream);
 
 /* The decompressed sizes of frames whose seek entries the caller does not hold: header walk + sequence walks on the device, no output
  * (a frame that carries Frame_Content_Size is walked all the same and held to it: corruption_detected when its blocks make another

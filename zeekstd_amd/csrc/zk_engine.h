@@ -7,7 +7,8 @@
 #include "zk_kernels.h"
 
 enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_EXEC, ZK_K_XXH64, ZK_K_STATUS,
-       ZK_K_ENC_MATCH, ZK_K_ENC_ENTROPY, ZK_K_ENC_COMPACT, ZK_K_ENC_XXH64, ZK_K_ENC_FSE_BUILD, ZK_K_ENC_DENSE, ZK_NKERNELS };
+       ZK_K_ENC_MATCH, ZK_K_ENC_ENTROPY, ZK_K_ENC_COMPACT, ZK_K_ENC_XXH64, ZK_K_ENC_FSE_BUILD, ZK_K_ENC_DENSE,
+       ZK_K_RANGE_PLAN, ZK_K_RANGE_PIECES, ZK_K_RANGE_GATHER, ZK_K_RANGE_STATUS, ZK_NKERNELS };
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };
@@ -30,6 +31,7 @@ struct zk_engine {
         hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_exec = nullptr;
         zk_devbuf infos, bases, words, blocks, seqs, lit, prog;     // prog: the executor's progress words (zk_k_xxh64_follow)
         zk_devbuf seg_tab, seg_cnt, seg_holes, seg_tiles;            // the executor in segments: ZkSeg records, per-frame / per-segment counts, hole records, tile counts
+        zk_devbuf rng, rng_meta;     // byte-range reads (zk_engine_ranges.hip): the decoded frames of one pass, the plan's arrays
         uint64_t *h_words = nullptr;
         bool ready = false;
         bool fused = false;          // the batch enqueued last took zk_k_entropy_frame
@@ -53,6 +55,8 @@ struct zk_engine {
     bool entropy_fused = false;      // the last finished decode ran zk_k_entropy_frame, not zk_k_huf || the sequence kernels (zk_engine_entropy_fused)
     int pipe_contexts = 0;           // host pipeline: decode contexts in flight (0 = default) and chunk size, zk_hostpipe_tune
     uint64_t pipe_chunk_bytes = 0;
+    uint64_t range_pass_bytes = 0;   // zk_read_ranges*: decoded bytes per pass (0 = ZK_RANGE_PASS_DEFAULT), ZK_CHOICE_RANGE_PASS_MIB
+    uint64_t ranges_frames = 0;      // frames the last zk_read_ranges* call decoded (zk_engine_ranges_frames_decoded)
     hipEvent_t ev_start[ZK_NKERNELS] = {}, ev_stop[ZK_NKERNELS] = {};
     bool ev_used[ZK_NKERNELS] = {};
     float kernel_ms[ZK_NKERNELS] = {};
@@ -100,7 +104,8 @@ zk_seek_table *zk_seek_table_from_cpp(const zeekstd::SeekTable *t);
 int zk_hostpipe_create(zk_engine *e);
 void zk_hostpipe_destroy(zk_engine *e);
 void zk_hostpipe_tune(zk_engine *e);                    // applies zk_engine::pipe_contexts / pipe_chunk_bytes (between calls)
-enum { ZK_HW_ENC_TOTAL = 8 };               // index into zk_engine::h_words of the encoder's total-size read-back
+enum { ZK_HW_ENC_TOTAL = 8, ZK_HW_RANGES = 10 };   // index into zk_engine::h_words of the encoder's total-size read-back; of the three words zk_read_ranges_dev reads back
+constexpr uint64_t ZK_RANGE_PASS_DEFAULT = 1ull << 30;
 struct zk_enc_args {
     const void *d_src; uint64_t n; uint32_t frame_size; int level, checksum;
     const void *d_prefix; uint64_t prefix_len; void *d_dst; uint64_t dst_cap; void *d_c_sizes, *d_d_sizes;

@@ -58,7 +58,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     if (!e) return ZK_ERR_ARGUMENT;
     ZkKernelChoice &k = e->choice;
     switch (what) {
-    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
+    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; e->range_pass_bytes = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
     case ZK_CHOICE_FSE_OWN: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; k.fse_own = value; return 0;
     case ZK_CHOICE_FSE_SHARED: if (value < 0 || value > 3) return ZK_ERR_ARGUMENT; k.fse_shared = value; return 0;
     case ZK_CHOICE_EXEC_LANES: if (value != 0 && value != 128 && value != 256 && value != 512 && value != 1024) return ZK_ERR_ARGUMENT; k.exec_lanes = value; return 0;
@@ -72,6 +72,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     case ZK_CHOICE_SEG_FILL: if (value < 0 || value > 3) return ZK_ERR_ARGUMENT; k.seg_fill = value; return 0;
     case ZK_CHOICE_PIPE_CONTEXTS: if (value < 0 || value > ZK_MAX_CTX) return ZK_ERR_ARGUMENT; e->pipe_contexts = value; zk_hostpipe_tune(e); return 0;
     case ZK_CHOICE_PIPE_CHUNK_MIB: if (value < 0 || value > 4096) return ZK_ERR_ARGUMENT; e->pipe_chunk_bytes = (uint64_t)value << 20; zk_hostpipe_tune(e); return 0;
+    case ZK_CHOICE_RANGE_PASS_MIB: if (value < 0 || value > (1 << 20)) return ZK_ERR_ARGUMENT; e->range_pass_bytes = (uint64_t)value << 20; return 0;
     default: return ZK_ERR_ARGUMENT;
     }
 }
@@ -82,7 +83,8 @@ extern "C" int zk_engine_kernel_count(void) { return ZK_NKERNELS; }
 extern "C" const char *zk_engine_kernel_name(int k)
 {
     static const char *names[ZK_NKERNELS] = {"zk_k_walk(count)", "zk_k_scan", "zk_k_walk(fill)", "zk_k_huf", "zk_k_fse", "zk_k_exec",
-                                             "zk_k_xxh64", "zk_k_status", "zk_k_enc_match", "zk_k_enc_entropy", "zk_k_enc_compact", "zk_k_enc_xxh64", "zk_k_enc_fse_build", "zk_k_enc_dense_cand"};
+                                             "zk_k_xxh64", "zk_k_status", "zk_k_enc_match", "zk_k_enc_entropy", "zk_k_enc_compact", "zk_k_enc_xxh64", "zk_k_enc_fse_build", "zk_k_enc_dense_cand",
+                                             "zk_k_range_plan", "zk_k_range_pieces", "zk_k_range_gather", "zk_k_range_status"};
     return k >= 0 && k < ZK_NKERNELS ? names[k] : "";
 }
 extern "C" int zk_engine_kernel_times(const zk_engine *e, float *ms_out, int n)
@@ -167,7 +169,7 @@ extern "C" void zk_engine_destroy(zk_engine *e)
     for (int k = 0; k < ZK_NKERNELS; k++) { if (e->ev_start[k]) (void)hipEventDestroy(e->ev_start[k]); if (e->ev_stop[k]) (void)hipEventDestroy(e->ev_stop[k]); }
     for (int i = 0; i < ZK_MAX_CTX; i++) {
         zk_engine::DecCtx &c = e->dctx[i];
-        for (zk_devbuf *b : {&c.infos, &c.bases, &c.words, &c.blocks, &c.seqs, &c.lit, &c.prog, &c.seg_tab, &c.seg_cnt, &c.seg_holes, &c.seg_tiles}) if (b->p) (void)hipFree(b->p);
+        for (zk_devbuf *b : {&c.infos, &c.bases, &c.words, &c.blocks, &c.seqs, &c.lit, &c.prog, &c.seg_tab, &c.seg_cnt, &c.seg_holes, &c.seg_tiles, &c.rng, &c.rng_meta}) if (b->p) (void)hipFree(b->p);
         if (c.h_words) (void)hipHostFree(c.h_words);
         for (hipEvent_t ev : {c.ev_fork, c.ev_join, c.ev_exec}) if (ev) (void)hipEventDestroy(ev);
         if (c.aux) (void)hipStreamDestroy(c.aux);

@@ -1,4 +1,4 @@
-// zk_kernels.h -- host-callable launchers of the gfx950 kernels (zk_decode.hip, zk_encode.hip)
+// zk_kernels.h -- host-callable launchers of the gfx950 kernels (zk_decode.hip, zk_encode.hip, zk_ranges.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "zk_device.h"
@@ -75,3 +75,21 @@ void zk_launch_enc_sizes(hipStream_t st, const ZkEncFrame *frames, uint32_t nfra
 void zk_launch_scan64(hipStream_t st, const uint64_t *in, uint32_t n, uint64_t *out);
 void zk_launch_enc_assemble(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint32_t nblocks, const ZkEncTables *ftab,
                             const uint8_t *lits, const uint8_t *scratch, const uint64_t *out_off, const uint64_t *c_size64, const uint64_t *hashes, int checksum, uint8_t *dst);
+
+// ---- byte-range reads (zk_ranges.hip; the per-range arithmetic: zk_ranges.h)
+struct ZkRangeArgs { const uint64_t *d_off; uint32_t n_frames; const uint64_t *offs, *lens, *dst_off; uint32_t count; void *dst; uint64_t dst_cap; };
+struct ZkRangeCopy { uint64_t src, dst, n; };           // n bytes from scratch + src to dst + dst: what one decode pass holds of a range
+constexpr uint64_t ZK_RANGE_SMALL = 16u << 10;          // copies up to here are a wave's, longer ones are dealt to workgroups in chunks of
+constexpr uint64_t ZK_RANGE_CHUNK = 64u << 10;
+// validation, first / last frame per range, the sorted unique touched frames (ids, uoff: n + 1 prefix sums of their sizes; slot: frame -> position) and
+// words[0..1] = their number and bytes.  r.dst_off == nullptr: the destinations are packed (prefix sums of the valid lengths, eff -> packed).  cover
+// (n_frames + 1 words) must be zero.
+void zk_launch_range_plan(hipStream_t st, const ZkRangeArgs &r, uint64_t *eff, uint64_t *packed, uint32_t *rfirst, uint32_t *rlast, int32_t *status, uint32_t *cover,
+                          uint32_t *slot, uint32_t *ids, uint64_t *uoff, uint64_t *words);
+void zk_launch_range_rebase(hipStream_t st, const uint64_t *uoff, uint32_t a, uint32_t n, uint64_t *poff);
+// the pass that holds positions [a, b) of the unique list: one copy per range (copies) and the chunk prefix sums of the large ones (cnt -> coff, count + 1)
+void zk_launch_range_pieces(hipStream_t st, const ZkRangeArgs &r, const uint64_t *dst_off, const uint32_t *rfirst, const uint32_t *rlast, const uint32_t *slot,
+                            const uint32_t *ids, const uint64_t *uoff, uint32_t a, uint32_t b, ZkRangeCopy *copies, uint64_t *cnt, uint64_t *coff);
+void zk_launch_range_gather(hipStream_t st, const uint8_t *scratch, uint8_t *dst, const ZkRangeCopy *copies, const uint64_t *coff, uint32_t count, uint64_t pass_bytes);
+void zk_launch_range_status(hipStream_t st, const ZkRangeArgs &r, const uint32_t *rfirst, const uint32_t *rlast, const uint32_t *slot, const int32_t *fstat,
+                            bool any_failed, const uint64_t *pass_err, int32_t *status, uint64_t *first_err);

@@ -56,7 +56,7 @@ class Engine:
 
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
-               "entropy": 13}
+               "entropy": 13, "range_pass_mib": 14}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -215,6 +215,42 @@ class Engine:
         if rc <= -1000:
             self._raise(rc)
         return rc
+
+    def read_ranges_dev(self, d_comp, comp_size, d_c_off, d_d_off, n_frames, d_offs, d_lens, d_dst_off, count, d_dst, dst_cap,
+                        verify=True, d_status=None, stream=None):
+        """Batched reads (zk_read_ranges_dev): bytes [d_offs[i], d_offs[i] + d_lens[i]) of the decompressed stream -> d_dst + d_dst_off[i]
+        (d_dst_off None: packed in list order); everything device-resident, uint64 arrays.  Returns 0 or the first failing range's status."""
+        rc = lib.zk_read_ranges_dev(self._h, self._ptr(d_comp), comp_size, self._ptr(d_c_off), self._ptr(d_d_off), n_frames,
+                                    self._ptr(d_offs), self._ptr(d_lens), self._ptr(d_dst_off) if d_dst_off is not None else None, count,
+                                    self._ptr(d_dst) if d_dst is not None else None, dst_cap, int(verify),
+                                    self._ptr(d_status) if d_status is not None else None, stream)
+        if rc <= -1000 and rc != -1001:
+            self._raise(rc)
+        return rc
+
+    def read_ranges(self, comp, c_off, d_off, offs, lens, verify=True, packed=False):
+        """Batched reads from host data (zk_read_ranges) -> (list of bytes, one per range -- b"" for a range that failed validation --, int32
+        status array).  packed=True: (one bytes object with the ranges back to back, uint64 offsets of count + 1 entries, status array)."""
+        comp = np.frombuffer(comp, dtype=np.uint8) if not isinstance(comp, np.ndarray) else comp
+        c_off, d_off, offs, lens = _u64(c_off), _u64(d_off), _u64(offs), _u64(lens)
+        count = len(offs)
+        total = int(d_off[-1])
+        ok = [int(o) <= total and int(n) <= total - int(o) for o, n in zip(offs, lens)]
+        pk = np.zeros(count + 1, np.uint64)
+        pk[1:] = np.cumsum([int(n) if k else 0 for n, k in zip(lens, ok)], dtype=np.uint64)
+        out = np.empty(max(int(pk[-1]), 1), np.uint8)
+        status = np.zeros(max(count, 1), np.int32)
+        rc = lib.zk_read_ranges(self._h, comp.ctypes.data, comp.size, c_off.ctypes.data, d_off.ctypes.data, len(d_off) - 1,
+                                offs.ctypes.data, lens.ctypes.data, None, count, out.ctypes.data, int(pk[-1]), int(verify), status.ctypes.data)
+        if rc <= -1000 and rc != -1001:
+            self._raise(rc)
+        if packed:
+            return out[:int(pk[-1])].tobytes(), pk, status[:count]
+        return [out[int(pk[i]):int(pk[i + 1])].tobytes() for i in range(count)], status[:count]
+
+    def ranges_frames_decoded(self):
+        """Frames the last read_ranges* call decoded, every touched frame once (zk_engine_ranges_frames_decoded)."""
+        return int(lib.zk_engine_ranges_frames_decoded(self._h))
 
     def xxh64_frames_dev(self, d_data, d_off, count, d_out, stream=None):
         rc = lib.zk_xxh64_frames_dev(self._h, self._ptr(d_data), self._ptr(d_off), count, self._ptr(d_out), stream)
