@@ -12,7 +12,17 @@ drawn at random, so that the decoders meet corners the libzstd-made goldens only
 
 It writes the bytes AND runs the sequences on a model of its own; what the frame MEANS is still decided by the real libzstd 1.5.7 in the tests that
 use it (tests/test_generated_frames.py: libzstd, the oracle, the lane code on the CPU; tests/test_gpu_generated_frames.py: the kernels) -- the
-model's output only has to agree with it, which checks the generator.  Nothing of the product imports this."""
+model's output only has to agree with it, which checks the generator.  Nothing of the product imports this.
+
+Keywords beyond the defaults (with the defaults a seed gives the bytes it always gave: every further draw sits behind its keyword):
+  stats=True       generate() also returns the facts of every block of the frame, in order, as dicts: type ("raw" | "rle" | "comp"), and for a
+                   compressed block lit ("raw" | "rle" | "huf" | "treeless"), streams (0 | 1 | 4), nlit, huf_depth and huf_def (the longest code of
+                   the tree the literals use and the index IN THE FRAME of the block that carries its description; None without Huffman), nseq,
+                   modes (the Symbol_Compression_Modes byte; None without sequences), ll_codes / ml_codes (sets), max_ll, max_ml, max_ml_off1
+  shared_tables    frames of 16 ... 80 blocks whose first block with sequences describes all three tables over every code the frame may use;
+                   later blocks mostly say Repeat_Mode (or Predefined_Mode) for all three, seldom redefine one table, use RLE_Mode or mix
+  max_ll / max_ml  upper ends of a long tail of literal lengths / match lengths (drawn by code, so the codes with 11 ... 16 extra bits come up),
+                   up to the block size; long matches mostly at offset 1.  max_lit has to allow the literals"""
 import random
 import struct
 
@@ -205,12 +215,14 @@ class HufCode:
 
 
 class FrameGen:
-    def __init__(self, seed, max_blocks=6, max_seq=300, max_lit=3000, prefix=b"", dense=False):
+    def __init__(self, seed, max_blocks=6, max_seq=300, max_lit=3000, prefix=b"", dense=False, shared_tables=False, max_ll=None, max_ml=None):
         self.rng = random.Random(seed)
         self.want_dense = dense                              # one block of the frame with more than 0x7F00 sequences
         self.prefix = bytes(prefix)                          # a raw-content prefix the frame is written against (ZSTD_CCtx_refPrefix): offsets reach into it
         self.max_blocks, self.max_seq, self.max_lit = max_blocks, max_seq, max_lit
         self.features = set()
+        self.shared, self.max_ll, self.max_ml = shared_tables, max_ll, max_ml
+        self.fact = {}                                       # the facts of the block being written (module docstring: stats=True)
 
     # ---- literals
     def literals_section(self, lits):
@@ -223,6 +235,7 @@ class FrameGen:
         if n >= 1 and self.huf is not None and all(x in self.huf.code for x in alphabet): kinds += ["treeless"] * 8
         kind = rng.choice(kinds)
         self.features.add("lit_" + kind)
+        self.fact.update(lit=kind, nlit=n, streams=0, huf_depth=None, huf_def=None)
         if kind in ("raw", "rle"):
             t = 0 if kind == "raw" else 1
             fmts = [f for f, cap in ((1, 1 << 12), (3, 1 << 20)) if n < cap] + ([0, 0] if n < 32 else [])
@@ -238,6 +251,7 @@ class FrameGen:
             d = huf.description(rng)
             if d is None: return None
             self.huf, desc = huf, d[0]
+            huf.block = self.block_index                     # (rides on the object: a block that is given up restores the code before it)
             self.features.add("huf_weights_" + d[1])
         else:
             desc = b""
@@ -252,6 +266,7 @@ class FrameGen:
             payload = desc + struct.pack("<HHH", *(len(p) for p in parts[:3])) + b"".join(parts)
             streams_fmt = [1, 2, 3]
         c = len(payload)
+        self.fact.update(streams=1 if one else 4, huf_depth=self.huf.maxbits, huf_def=self.huf.block)
         fmts = [f for f in streams_fmt if (f <= 1 and n < 1024 and c < 1024) or (f == 2 and n < 16384 and c < 16384) or (f == 3 and n < (1 << 18) and c < (1 << 18))]
         if not fmts: return None
         f = rng.choice(fmts)
@@ -263,8 +278,9 @@ class FrameGen:
         return hdr + payload
 
     # ---- sequences
-    def table_for(self, which, codes, nsym, al_lo, al_hi, default, default_al):
-        """-> (mode, description bytes, cells, accuracy log) for the table `which` given the codes this block uses"""
+    def table_for(self, which, codes, nsym, al_lo, al_hi, default, default_al, want=None, full=None):
+        """-> (mode, description bytes, cells, accuracy log) for the table `which` given the codes this block uses.
+        want (shared_tables): the mode to take if the codes allow it, FSE_Compressed otherwise; full: the codes a description then covers"""
         rng = self.rng
         modes = []
         if all(c < len(default) and default[c] != 0 for c in codes): modes += [0, 0]
@@ -272,7 +288,10 @@ class FrameGen:
         modes += [2, 2]
         prev = self.tables.get(which)
         if prev is not None and all(any(cell[0] == c for cell in prev[0]) for c in set(codes)): modes += [3, 3]
-        mode = rng.choice(modes)
+        if want is None: mode = rng.choice(modes)
+        else:
+            mode = want if want in modes else 2
+            if mode == 2: codes = sorted(set(codes) | set(full))
         self.features.add("%s_mode%d" % (which, mode))
         if mode == 0: cells, al, desc = fse_cells(default, default_al), default_al, b""
         elif mode == 1: cells, al, desc = [(codes[0], 0, 0)], 0, bytes([codes[0]])
@@ -284,10 +303,23 @@ class FrameGen:
         self.tables[which] = (cells, al)
         return mode, desc, cells, al
 
+    def shared_wants(self):
+        """shared_tables: the three modes this block would like (table_for takes FSE_Compressed over all codes where the block's codes forbid one)"""
+        rng = self.rng
+        if not self.tables: return [2, 2, 2]                 # the frame's first block with sequences describes all three
+        r = rng.random()
+        if r < 0.90: return [3, 3, 3]
+        if r < 0.93: return [0, 0, 0]                         # (a Repeat_Mode behind it repeats the predefined table)
+        if r < 0.96: return [rng.choice([0, 3]) for _ in range(3)]
+        w = [3, 3, 3]
+        w[rng.randrange(3)] = 2 if r < 0.98 else 1
+        return w
+
     def sequences_section(self, seqs):
         """seqs: [(ll, ml, offset_value)] -> bytes"""
         rng = self.rng
         n = len(seqs)
+        self.fact.update(nseq=n, modes=None, ll_codes=set(), ml_codes=set(), max_ll=max([s[0] for s in seqs], default=0), max_ml=max([s[1] for s in seqs], default=0))
         if n == 0: return b"\x00"
         form = 3 if n >= 0x7F00 else 2 if n >= 128 else rng.choice([1, 1, 1, 2])       # (the two-byte form may carry a small count)
         if form == 1: hdr = bytes([n])
@@ -300,9 +332,11 @@ class FrameGen:
         for s in seqs:
             c = s[2].bit_length() - 1
             of.append((c, s[2] - (1 << c), c))
-        m_ll, d_ll, c_ll, a_ll = self.table_for("ll", [x[0] for x in ll], 36, 5, 9, LL_DEF, 6)
-        m_of, d_of, c_of, a_of = self.table_for("of", [x[0] for x in of], 32, 5, 8, OF_DEF, 5)
-        m_ml, d_ml, c_ml, a_ml = self.table_for("ml", [x[0] for x in ml], 53, 5, 9, ML_DEF, 6)
+        wants, full = self.shared_wants() if self.shared else (None, None, None), (range(36), range(self.of_codes), range(53))
+        m_ll, d_ll, c_ll, a_ll = self.table_for("ll", [x[0] for x in ll], 36, 5, 9, LL_DEF, 6, wants[0], full[0])
+        m_of, d_of, c_of, a_of = self.table_for("of", [x[0] for x in of], 32, 5, 8, OF_DEF, 5, wants[1], full[1])
+        m_ml, d_ml, c_ml, a_ml = self.table_for("ml", [x[0] for x in ml], 53, 5, 9, ML_DEF, 6, wants[2], full[2])
+        self.fact.update(modes=(m_ll << 6) | (m_of << 4) | (m_ml << 2), ll_codes={x[0] for x in ll}, ml_codes={x[0] for x in ml})
 
         def chain(cells, codes):
             """states[i] of a decoder that sees codes[i] in state i, and the bits that take it from i to i + 1"""
@@ -339,17 +373,28 @@ class FrameGen:
         else: alpha = bytes(rng.sample(range(0, rng.choice([129, 256])), rng.randint(1, rng.choice([2, 6, 40, 100])))) if rng.random() < 0.8 else bytes(range(256))
         self.alpha = alpha
         lits, seqs = bytearray(), []
-        produced = 0
+        produced = max_ml_off1 = 0
         start = len(out)
         for _ in range(nseq):
             ll = 0 if rng.random() < 0.3 else rng.choice([rng.randint(1, 8), rng.randint(1, 40), rng.randint(1, 2000 if style < 0.1 else 60)])
             ml = rng.choice([3, rng.randint(3, 12), rng.randint(3, 130), rng.randint(3, 3000 if style < 0.1 else 200)])
             if dense: ll, ml = (1 if rng.random() < 0.02 else 0), (3 if rng.random() < 0.9 else 4)
+            off1 = False
+            if self.max_ll is not None and rng.random() < 0.08:          # the long tail, by code: 16 ... 35, cut to what the block still holds
+                c = rng.choice([rng.randint(16, 35), rng.randint(27, 35), 35])
+                ll = min(LL_BASE[c] + rng.randrange(1 << LL_BITS[c]), self.max_ll, self.max_lit - len(lits), block_max - produced - 3)
+                if ll < 0: break
+            if self.max_ml is not None and rng.random() < 0.08:          # codes 32 ... 52
+                c = rng.choice([rng.randint(32, 52), rng.randint(46, 52), 52])
+                ml = min(ML_BASE[c] + rng.randrange(1 << ML_BITS[c]), self.max_ml, block_max - produced - ll)
+                if ml < 3: break
+                off1 = rng.random() < 0.6
             if len(lits) + ll > self.max_lit or produced + ll + ml > block_max: break
             here = len(self.prefix) + len(out) + ll           # bytes available behind the literals
             reach = min(here, window)                         # (an offset beyond the window into a prefix: libzstd takes it until its ring wraps -- not valid zstd, not drawn)
-            r = rng.random()
+            r = rng.random() if not (off1 and here) else 1.0
             ofv = None
+            if off1 and here: off, ofv = 1, 4                 # (a long match of one byte's run)
             if r < 0.45:                                      # a repeat code
                 code = rng.randint(1, 3)
                 idx = code - 1 + (1 if ll == 0 else 0)
@@ -376,12 +421,14 @@ class FrameGen:
                 out.append(out[i] if i >= 0 else self.prefix[len(self.prefix) + i])
             produced += ll + ml
             seqs.append((ll, ml, ofv))
+            if off == 1: max_ml_off1 = max(max_ml_off1, ml)
         tail = rng.randint(0, min(self.max_lit - len(lits), block_max - produced, rng.choice([0, 5, 300, 3000])))
         new = bytes(rng.choice(alpha) for _ in range(tail))
         lits += new; out += new
         lit = self.literals_section(lits)
         if lit is None: return None, rep
         body = lit + self.sequences_section(seqs)
+        self.fact.update(max_ml_off1=max_ml_off1)
         if len(body) > block_max or len(body) >= (1 << 21): return None, rep
         return body, rep
 
@@ -394,29 +441,35 @@ class FrameGen:
             self.max_off = 0
             self.dense = self.want_dense
             exp, mant = rng.choice([0, 0, 1, 3, 7, rng.randint(0, 10)]), rng.randint(0, 7)
+            if (self.max_ll is not None or self.max_ml is not None) and rng.random() < 0.7: exp = rng.randint(7, 10)     # blocks of 128 KiB
             window = (1 << (10 + exp)) + ((1 << (10 + exp)) >> 3) * mant
             block_max = min(window, 1 << 17)
+            self.of_codes = (window + 3).bit_length()         # offset codes 0 ... log2 of the largest Offset_Value
             out, rep = bytearray(), [1, 4, 8]
-            blocks = []
+            blocks, facts = [], []
             ok = True
-            for _ in range(rng.randint(1, self.max_blocks)):
+            nblocks = rng.randint(16, 80) if self.shared else rng.randint(1, self.max_blocks)
+            for _ in range(2 * nblocks if self.shared else nblocks):        # (shared_tables: a block that is given up is drawn again)
+                if len(blocks) == nblocks: break
                 r = rng.random()
+                self.block_index = len(blocks)
                 if r < 0.15:
                     n = rng.choice([0, rng.randint(0, 40), rng.randint(0, min(block_max, 5000))])
                     data = bytes(rng.randrange(256) for _ in range(n))
-                    blocks.append((0, n, data)); out += data; self.features.add("raw")
+                    blocks.append((0, n, data)); out += data; self.features.add("raw"); facts.append({"type": "raw"})
                 elif r < 0.3:
                     n = rng.choice([0, 1, rng.randint(0, 300), rng.randint(0, block_max)])
                     v = rng.randrange(256)
-                    blocks.append((1, n, bytes([v]))); out += bytes([v]) * n; self.features.add("rle")
+                    blocks.append((1, n, bytes([v]))); out += bytes([v]) * n; self.features.add("rle"); facts.append({"type": "rle"})
                 else:
                     snap = (len(out), list(rep), self.huf, dict(self.tables))
+                    self.fact = {"type": "comp"}
                     body, rep2 = self.compressed_block(out, rep, window, block_max)
                     if body is None:
                         del out[snap[0]:]; rep, self.huf, self.tables = snap[1], snap[2], snap[3]
                         continue
                     rep = rep2
-                    blocks.append((2, len(body), body)); self.features.add("compressed")
+                    blocks.append((2, len(body), body)); self.features.add("compressed"); facts.append(self.fact)
             if not blocks or self.dense: continue               # (a dense block was asked for and did not come about: window too small, ...)
             total = len(out)
             # Single_Segment: the window IS the content size, and Block_Maximum_Size follows it -- also for what a block holds
@@ -441,14 +494,24 @@ class FrameGen:
             body = bytearray()
             for i, (t, n, payload) in enumerate(blocks):
                 body += ((n << 3) | (t << 1) | (1 if i + 1 == len(blocks) else 0)).to_bytes(3, "little") + payload
+            self.facts = facts
             return bytes(hdr + body), bytes(out), cks, set(self.features)
 
 
-def generate(seed, xxh64=None, **kw):
-    """-> (frame bytes, decoded bytes, features).  xxh64: the caller's hash function (this file has none) -- without one no frame gets a checksum"""
-    f, out, cks, feats = FrameGen(seed, **kw).frame()
+def generate(seed, xxh64=None, stats=False, **kw):
+    """-> (frame bytes, decoded bytes, features) and, with stats=True, the facts of every block (module docstring).
+    xxh64: the caller's hash function (this file has none) -- without one no frame gets a checksum"""
+    g = FrameGen(seed, **kw)
+    f, out, cks, feats = g.frame()
     if cks and xxh64 is not None:
         f += (xxh64(out) & 0xFFFFFFFF).to_bytes(4, "little")
     elif cks:
         f = f[:4] + bytes([f[4] & ~4]) + f[5:]
-    return f, out, feats | ({"checksum"} if cks and xxh64 is not None else set())
+    feats = feats | ({"checksum"} if cks and xxh64 is not None else set())
+    return (f, out, feats, g.facts) if stats else (f, out, feats)
+
+
+def own_blocks(facts):
+    """blocks whose modes byte has a table in RLE_Mode or FSE_Compressed_Mode (the two bits of its field differ): what the engine counts as
+    a frame's n_own_tables"""
+    return sum(1 for b in facts if b.get("modes") is not None and (b["modes"] ^ (b["modes"] >> 1)) & 0x54)

@@ -8,6 +8,7 @@ import collections
 import pytest
 
 from conftest import sim_decode
+from helpers import gen_batches as G
 from helpers import zstd_gen
 from oracle import zko
 from oracle import libzstd_ref as Z
@@ -149,3 +150,95 @@ def test_damaged_generated_frames_the_lane_code_against_the_oracle(quad):
             assert out[lo:hi] == o, f
         refused += not ok
     assert refused > 50
+
+
+# ---- the keywords behind tests/test_gpu_generated_variants.py, on the very seeds it decodes (tests/helpers/gen_batches.py)
+def test_default_arguments_keep_their_bytes():
+    """every draw of the new keywords sits behind its keyword: a default frame's bytes are what they were (XXH64 of the first 200 seeds' frames,
+    recorded before the keywords existed), and stats=True changes nothing but the return value"""
+    h = zko.xxh64(b"".join(zstd_gen.generate(seed, zko.xxh64)[0] for seed in range(200)))
+    assert h == 0xA102EF72F9DCAE2E
+    for seed in (0, 7, 123):
+        assert zstd_gen.generate(seed, zko.xxh64, stats=True)[:3] == zstd_gen.generate(seed, zko.xxh64)
+
+
+@pytest.mark.parametrize("kind,seeds", [("shared", G.SHARED_SEEDS), ("tail", G.TAIL_SEEDS)], ids=["shared_tables", "max_ll_max_ml"])
+def test_new_keywords_mean_what_libzstd_says(kind, seeds):
+    """shared_tables and max_ll / max_ml through libzstd 1.5.7 (the judge), the oracle, the lane code in all three sequence walks and the
+    executor in segments"""
+    ref = "1.5.7" if Z.load("1.5.7") is not None else "system"
+    if Z.load(ref) is None:
+        pytest.skip("no libzstd in the image")
+    for f in G.frames(seeds, kind):
+        assert Z.decode_stream_verdict(f.comp, ref) == (f.data, "end"), f.seed
+        o, used = zko.frame_decode(f.comp, len(f.data) + 64, True)
+        assert used == len(f.comp) and o == f.data, f.seed
+        for quad in (False, True, 2):
+            rc, so, st = sim_decode(f.comp, [(len(f.comp), len(f.data))], quad=quad)
+            assert rc == 0 and so == f.data, (f.seed, quad)
+        for seg in ((131072, 64, 2), (1 + f.seed % 5000, 3 + f.seed % 200, 2), (65536, 1024, 1), (131072, 256, 1), (700 + f.seed % 3000, 16, 2)):
+            rc, so, st = sim_decode(f.comp, [(len(f.comp), len(f.data))], seg=seg)
+            assert rc == 0 and so == f.data, (f.seed, seg)
+        assert len(f.facts) >= (16 if kind == "shared" else 1)
+
+
+def test_the_gpu_tests_seeds_reach_what_they_are_for():
+    """what the generator could not draw before, on the seeds the GPU tests use: every Literals_Length code 0 ... 35 and every Match_Length
+    code 0 ... 52 (the ones with 11 ... 16 extra bits among them), a match of more than 65 538 bytes at offset 1, a literal run of 65 536 and
+    more, Huffman trees of depth 11, Treeless literals whose tree was described in another group of 16 blocks of the batch"""
+    tail = G.blocks_of(G.frames(G.TAIL_SEEDS, "tail"))
+    ll, ml = set(), set()
+    for b in tail:
+        ll |= b.get("ll_codes", set()); ml |= b.get("ml_codes", set())
+    for b in G.blocks_of(G.frames(G.SHARED_SEEDS, "shared")):
+        ll |= b.get("ll_codes", set()); ml |= b.get("ml_codes", set())
+    assert ll == set(range(36)), set(range(36)) - ll
+    assert ml == set(range(53)), set(range(53)) - ml
+    assert max(b.get("max_ml_off1", 0) for b in tail) > 65538
+    assert max(b.get("max_ll", 0) for b in tail) >= 65536
+    for name in ("shared", "huffman"):
+        blocks = G.blocks_of(getattr(G, "batch_" + name)())
+        assert any(g.depths.count(11) >= 3 for g in G.huf_groups(blocks)), name
+        other_group, other_run = G.treeless_reach(blocks)
+        assert other_group > 0 and other_run > 0, name
+
+
+def test_block_facts_against_the_device_walk():
+    """the facts a GPU test computes its premises from are the generator's own account (generate(..., stats=True)); the block walker of
+    tests/helpers/enc_inputs.py reads the same block types, literal types and sizes, Huffman depths, sequence counts and modes bytes back
+    from the frame's BYTES wherever it knows the header forms, and the same count of own blocks by zk_device.h's rule,
+    (m ^ (m >> 1)) & 0x54 on the modes byte"""
+    from helpers import enc_inputs
+    seen = 0
+    for f in G.frames(G.DEFAULT_SEEDS[:300]):
+        try:
+            walked = enc_inputs.walk_frame(f.comp)
+        except AssertionError:
+            continue                                         # Treeless literals, FSE-compressed weights, RLE_Mode tables: not that walker's
+        assert [b["type"] for b in walked] == [b["type"] for b in f.facts], f.seed
+        for w, b in zip(walked, f.facts):
+            if w["type"] == "comp":
+                assert (w["nseq"], w["modes"], w["nlit"], w["lit"]) == (b["nseq"], b["modes"], b["nlit"], b["lit"]), f.seed
+                if w["lit"] == "huf":
+                    assert w["huf_depth"] == b["huf_depth"], f.seed
+        assert f.own == sum(1 for w in walked if w.get("modes") and (w["modes"] ^ (w["modes"] >> 1)) & 0x54)
+        seen += 1
+    assert seen > 60
+
+
+def test_dense_frames_overflow_their_segments():
+    """The premise of tests/test_gpu_generated_variants.py, test_generated_frames_in_segments: the dense frames it decodes have more hole
+    records than a segment's region of out/4 + 8 holds (cap_shift = 2, the device's), with segments of 32 KiB and of 1 KiB -- the frame is
+    given up and executed again by the frame executor (the simulator counts it), and the bytes are the model's.  A frame that is ONE
+    segment of 128 KiB does not overflow."""
+    import ctypes as C
+    from conftest import sim_lib
+    a = (C.c_uint64 * 4)()
+    for f in G.frames(G.DENSE_SEEDS, "dense"):
+        for seg_bytes, redone in ((32768, True), (1024, True), (131072, False)):
+            sim_lib().zk_sim_seg_stats(a, 1)
+            rc, out, st = sim_decode(f.comp, [(len(f.comp), len(f.data))], seg=(seg_bytes, 64, 2))
+            assert rc == 0 and not st.any() and out == f.data, (f.seed, seg_bytes)
+            sim_lib().zk_sim_seg_stats(a, 1)
+            assert (a[3] > 0) == redone, (f.seed, seg_bytes, list(a))
+

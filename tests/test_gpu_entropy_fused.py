@@ -8,54 +8,13 @@ import numpy as np
 import pytest
 
 from conftest import GOLDENS, offsets_from_frames
+from helpers.dev_decode import both as _both, dev as _dev, upload as _upload
 from oracle import zko
 from oracle import libzstd_ref as Z
 
 pytestmark = pytest.mark.gpu
 
 FRAME = 2 << 20
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _upload(comp, c, d):
-    import torch
-    dev = _dev()
-    return (torch.from_numpy(np.frombuffer(bytes(comp) + b"\0" * 64, np.uint8).copy()).to(dev), len(comp),
-            torch.from_numpy(np.asarray(c, np.uint64).view(np.int64).copy()).to(dev), torch.from_numpy(np.asarray(d, np.uint64).view(np.int64).copy()).to(dev))
-
-
-def _decode(engine, setting, arch, nf, total, d_out=None):
-    """-> (rc, output tensor, statuses, whether the fused kernel ran) with ZK_CHOICE_ENTROPY = setting"""
-    import torch
-    d_comp, csize, d_c, d_d = arch
-    if d_out is None:
-        d_out = torch.empty(total + 64, dtype=torch.uint8, device=_dev())
-    d_out.zero_()
-    d_st = torch.full((nf,), -1, dtype=torch.int32, device=_dev())
-    engine.set_kernel_choice(reset=0)
-    try:
-        engine.set_kernel_choice(entropy=setting)
-        rc = engine.decode_frames_dev(d_comp, csize, d_c, d_d, 0, nf, d_out, total, True, d_st)
-        fused = engine.entropy_fused()
-    finally:
-        engine.set_kernel_choice(reset=0)
-    torch.cuda.synchronize()
-    return rc, d_out, d_st.cpu().numpy(), fused
-
-
-def _both(engine, arch, nf, total, same_bytes=True):
-    import torch
-    rc1, o1, st1, f1 = _decode(engine, 1, arch, nf, total)
-    rc2, o2, st2, f2 = _decode(engine, 2, arch, nf, total)
-    assert not f1, "ZK_CHOICE_ENTROPY = 1 is the two kernels"
-    assert rc1 == rc2 and np.array_equal(st1, st2)
-    if same_bytes:
-        assert torch.equal(o1[:total], o2[:total])
-    return rc2, o2, st2, f2
 
 
 def test_choice_values(engine):
