@@ -190,6 +190,34 @@ int zk_decode_frames_prefix(zk_engine *e, const uint8_t *comp, uint64_t comp_siz
                             const uint64_t *d_off, uint32_t first, uint32_t count, const uint8_t *prefix, uint64_t prefix_len,
                             uint8_t *dst, uint64_t dst_cap, int verify, int32_t *frame_status);
 
+/* Decode frames that were compressed with a zstd dictionary (what the reference reaches through DecodeOptions::with_dctx, decode.rs:43,
+ * with a context the caller has loaded a dictionary into; ZSTD_DCtx_loadDictionary).
+ * zk_dict_create parses and validates the bytes on the host (no GPU needed) and copies them.  Bytes that begin with 0xEC30A437 are a
+ * formatted dictionary (RFC 8878 section 5: magic, Dictionary_ID, Huffman tree description, FSE descriptions of offsets, match lengths and
+ * literal lengths, three repeat offsets, content); -30 (dictionary_corrupted) when its entropy section is truncated or invalid or a
+ * repeat offset is 0 or larger than the content.  Anything else is a raw-content dictionary: ID 0, no tables, repeat offsets 1 / 4 / 8, every
+ * byte content.  Content beyond 2^30 - 2^27 bytes: -16, as for a prefix.
+ * zk_engine_set_dictionary uploads the dictionary once (the engine keeps its own device copy: the zk_dict may be freed right away);
+ * NULL = none.  ZK_ERR_ARGUMENT while a submitted batch is outstanding (zk_decode_wait first).  With a dictionary set, every frame of
+ * zk_decode_frames[_dev], zk_decode_frame_list_dev, zk_decode_submit_dev, zk_read_ranges[_dev], zk_frame_content_sizes[_dev],
+ * zk_decode_shard and of the zk_decoder_* handles opened on the engine is decoded as libzstd decodes it after loadDictionary:
+ *   - a Dictionary_ID field that is absent, 0 or the dictionary's is accepted, any other value is -32 for that frame alone;
+ *   - the dictionary's content lies right before the frame's first byte (offsets are bounded by availability, as with a prefix) and
+ *     the repeat-offset history starts from the dictionary's three offsets;
+ *   - formatted dictionaries: the Huffman tree and the three sequence tables in force at the frame's first block are the dictionary's
+ *     (Treeless literals / Repeat_Mode there are valid); with a raw-content dictionary, or none, they stay corruption (-20).
+ * An explicit non-empty prefix (zk_decode_frames_prefix*, zk_decoder_decompress_with_prefix) overrides the dictionary for that call, as
+ * ZSTD_DCtx_refPrefix does.  As in libzstd, EVERY frame of the call starts from the dictionary's repeat offsets and has its content below it: a frame that was made without
+ * a dictionary decodes to the same bytes unless it uses a repeat offset before it has set one (libzstd's encoder emits no such frame) and the
+ * dictionary's offsets are not 1 / 4 / 8, or it is damaged.  Encoding against a
+ * dictionary is not offered. */
+typedef struct zk_dict zk_dict;
+int zk_dict_create(const uint8_t *bytes, size_t len, zk_dict **out);
+void zk_dict_free(zk_dict *d);
+uint32_t zk_dict_id(const zk_dict *d);             /* 0 for a raw-content dictionary */
+size_t zk_dict_content_offset(const zk_dict *d);   /* 0 for raw content, else the first byte of Content */
+int zk_engine_set_dictionary(zk_engine *e, const zk_dict *d);
+
 /* The decompressed sizes of frames whose seek entries the caller does not hold: header walk + sequence walks on the device, no output
  * (a frame that carries Frame_Content_Size is walked all the same and held to it: corruption_detected when its blocks make another
  * size).  What libzstd's streaming decoder needs no table for

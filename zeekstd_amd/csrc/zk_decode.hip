@@ -32,10 +32,19 @@
 // that do not come from a SeekTable (arbitrary caller arrays) cannot drive reads or writes out of bounds.
 __global__ __launch_bounds__(64) void zk_k_walk(const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off, const uint64_t *d_off,
                                                 uint32_t first, uint32_t count, const uint32_t *ids, const uint64_t *out_off, uint64_t dst_cap,
-                                                const ZkFrameBase *bases, ZkBlock *blocks, ZkFrameInfo *infos)
+                                                const ZkFrameBase *bases, ZkBlock *blocks, ZkFrameInfo *infos, ZkWalkDict wd)
 {
     uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= count) return;
+    // a dictionary is loaded (zk_dict.h): its ID and where its tables are described -- the block entry behind the batch's last block,
+    // which the fill pass writes; its "content" lies outside the compressed buffer, src says how far
+    ZkDictWalk dw; dw.on = wd.on; dw.id = wd.id; dw.def = wd.def;
+    if (bases && f == 0 && wd.tmpl) {
+        ZkBlock t = *wd.tmpl;
+        t.src = (uint64_t)(uintptr_t)wd.img - (uint64_t)(uintptr_t)comp;
+        t.huf_def = wd.def; t.tab_def[0] = wd.def; t.tab_def[1] = wd.def; t.tab_def[2] = wd.def;
+        blocks[wd.def] = t;
+    }
     const uint32_t id = ids ? ids[f] : first + f;
     uint64_t cb = c_off[id], ce = c_off[id + 1];
     // d_off == nullptr (zk_frame_content_sizes): nobody knows the frames' sizes yet, nothing is written
@@ -43,7 +52,7 @@ __global__ __launch_bounds__(64) void zk_k_walk(const uint8_t *comp, uint64_t co
     ZkFrameInfo fi;
     if (!bases && !d_off) {
         if (ce < cb || ce > comp_size) { fi.n_blocks = 0; fi.n_seq = 0; fi.lit_bytes = 0; fi.status = ZK_E_SRC_SIZE_WRONG; fi.checksum_flag = 0; fi.checksum = 0; fi.window = 0; fi.n_own_tables = 0; fi.fcs = ZK_SIZE_UNKNOWN; }
-        else zk_walk_frame(comp, cb, ce, dsz, f, nullptr, nullptr, fi);
+        else zk_walk_frame(comp, cb, ce, dsz, f, nullptr, nullptr, fi, dw);
         if (fi.status != ZK_OK) { fi.n_blocks = 0; fi.n_seq = 0; fi.lit_bytes = 0; }
         infos[f] = fi;
     } else if (!bases) {                            // pass 1: count
@@ -54,14 +63,14 @@ __global__ __launch_bounds__(64) void zk_k_walk(const uint8_t *comp, uint64_t co
             infos[f] = fi;
             return;
         }
-        zk_walk_frame(comp, cb, ce, dsz, f, nullptr, nullptr, fi);
+        zk_walk_frame(comp, cb, ce, dsz, f, nullptr, nullptr, fi, dw);
         if (fi.status == ZK_OK && (d_off[id] < d_off[first] && !out_off)) fi.status = ZK_E_SRC_SIZE_WRONG;
         if (fi.status == ZK_OK && (o > dst_cap || dsz > dst_cap - o)) fi.status = ZK_E_DST_TOO_SMALL;
         if (dsz > ZK_MAX_FRAME && fi.status == ZK_OK) fi.status = ZK_E_FRAMEPARAM_UNSUPPORTED;
         if (fi.status != ZK_OK) { fi.n_blocks = 0; fi.n_seq = 0; fi.lit_bytes = 0; }   // contributes no work
         infos[f] = fi;
     } else if (infos[f].status == ZK_OK) {          // pass 2: fill the block list
-        zk_walk_frame(comp, cb, ce, dsz, f, &bases[f], blocks, fi);
+        zk_walk_frame(comp, cb, ce, dsz, f, &bases[f], blocks, fi, dw);
     }
 }
 
@@ -581,8 +590,11 @@ __device__ __forceinline__ ZkFsePick zk_fse_share_pick(uint32_t nblocks, uint32_
     const int ref = cm ? __builtin_ctzll(cm) : 0;
     p.r0 = __shfl(p.k0, ref, 64); p.r1 = __shfl(p.k1, ref, 64); p.r2 = __shfl(p.k2, ref, 64);
     p.match = cand && p.k0 == p.r0 && p.k1 == p.r1 && p.k2 == p.r2;
-    const bool predef = p.r0 == ZK_KEY_PREDEF && p.r1 == ZK_KEY_PREDEF && p.r2 == ZK_KEY_PREDEF;
-    p.go = cm != 0 && (predef || (uint32_t)__popcll(__ballot(p.match)) >= ZK_FSEP_MIN_SHARE);
+    // keys that no block of the batch owns -- ZK_KEY_PREDEF, and the entry of a loaded dictionary (index nblocks, zk_dict.h) -- are
+    // worth a shared copy however few lanes carry them.  (0xFFFFFFFF, "no table in force", never gets here: the walk refuses a frame whose
+    // block repeats a table nobody defined, and a refused frame's blocks are no candidates)
+    const bool unowned = p.r0 >= nblocks && p.r1 >= nblocks && p.r2 >= nblocks;
+    p.go = cm != 0 && (unowned || (uint32_t)__popcll(__ballot(p.match)) >= ZK_FSEP_MIN_SHARE);
     return p;
 }
 // the reference's three tables (called by 16 lanes redundantly: identical LDS writes, >= 16 active lanes)
@@ -833,8 +845,8 @@ __device__ __forceinline__ ZkFsePickSets zk_fse_share_pick_sets(uint32_t nblocks
         const uint32_t r0 = __shfl(p.k0, ref, 64), r1 = __shfl(p.k1, ref, 64), r2 = __shfl(p.k2, ref, 64);
         const bool m = cand && p.k0 == r0 && p.k1 == r1 && p.k2 == r2;
         const uint64_t mm = __ballot(m);
-        const bool predef = r0 == ZK_KEY_PREDEF && r1 == ZK_KEY_PREDEF && r2 == ZK_KEY_PREDEF;
-        if (predef || (uint32_t)__popcll(mm) >= ZK_FSEP_MIN_SHARE) { if (m) p.set = (int32_t)p.nsets; p.nsets++; }
+        const bool unowned = r0 >= nblocks && r1 >= nblocks && r2 >= nblocks;     // (as zk_fse_share_pick)
+        if (unowned || (uint32_t)__popcll(mm) >= ZK_FSEP_MIN_SHARE) { if (m) p.set = (int32_t)p.nsets; p.nsets++; }
         rem &= ~mm;
     }
     return p;
@@ -1016,7 +1028,7 @@ __global__ __launch_bounds__(T) ZK_EXEC_WPE(T) void zk_k_exec(const uint8_t *__r
                                                const ZkBlock *__restrict__ blocks, const ZkFrameBase *__restrict__ bases,
                                                ZkFrameInfo *__restrict__ infos, const ZkSeqP *__restrict__ seqs,
                                                const uint8_t *__restrict__ lit_scratch, uint8_t *__restrict__ dst,
-                                               const uint8_t *__restrict__ prefix, uint64_t plen, uint64_t *__restrict__ progress)
+                                               const uint8_t *__restrict__ prefix, uint64_t plen, uint64_t *__restrict__ progress, ZkRepInit rep0)
 {
     // The staged sequences live in an LDS RING of CAP records, slot = block sequence index & (CAP - 1).  A tile retires the
     // jn sequences it has consumed and exactly as many new ones are fetched for the tiles to come -- requested right after
@@ -1047,7 +1059,8 @@ __global__ __launch_bounds__(T) ZK_EXEC_WPE(T) void zk_k_exec(const uint8_t *__r
     uint8_t *out = dst + zk_uni((uint64_t)(out_off ? out_off[f] : d_off[id] - d_off[first]));     // indexed batches are packed in list order
     const ZkBlock *fb = blocks + zk_uni((uint64_t)bases[f].block_base);
     uint64_t pos = 0;
-    uint32_t rep[3] = {1, 4, 8};
+    // (a dictionary's content is a prefix, and its three offsets are the history a frame starts with: zk_dict.h)
+    uint32_t rep[3] = {PFX ? rep0.r[0] : 1u, PFX ? rep0.r[1] : 4u, PFX ? rep0.r[2] : 8u};
     uint32_t err = ZK_OK;
     const uint32_t block_max = fi.window < ZK_BLOCK_MAX ? fi.window : ZK_BLOCK_MAX;
 #ifdef ZK_EXEC_CLOCKS
@@ -2637,9 +2650,10 @@ void zk_launch_status(hipStream_t st, const ZkFrameInfo *infos, uint32_t count, 
     hipLaunchKernelGGL(zk_k_status, dim3((count + 255) / 256), dim3(256), 0, st, infos, count, status_out, (unsigned long long *)first_err, progress, (unsigned long long *)followed);
 }
 void zk_launch_walk(hipStream_t st, const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off, const uint64_t *d_off, uint32_t first,
-                    uint32_t count, const uint32_t *ids, const uint64_t *out_off, uint64_t dst_cap, const ZkFrameBase *bases, ZkBlock *blocks, ZkFrameInfo *infos)
+                    uint32_t count, const uint32_t *ids, const uint64_t *out_off, uint64_t dst_cap, const ZkFrameBase *bases, ZkBlock *blocks, ZkFrameInfo *infos,
+                    const ZkWalkDict &wd)
 {
-    hipLaunchKernelGGL(zk_k_walk, dim3((count + 63) / 64), dim3(64), 0, st, comp, comp_size, c_off, d_off, first, count, ids, out_off, dst_cap, bases, blocks, infos);
+    hipLaunchKernelGGL(zk_k_walk, dim3((count + 63) / 64), dim3(64), 0, st, comp, comp_size, c_off, d_off, first, count, ids, out_off, dst_cap, bases, blocks, infos, wd);
 }
 void zk_launch_frame_sizes(hipStream_t st, const ZkFrameInfo *infos, const ZkFrameBase *bases, const ZkBlock *blocks, uint32_t count, uint64_t *sizes, int32_t *status_out)
 {
@@ -2654,7 +2668,7 @@ void zk_launch_huf(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_
     if (!nblocks) return;
     hipLaunchKernelGGL(zk_k_huf, dim3((nblocks + ZK_HUF_BLOCKS - 1) / ZK_HUF_BLOCKS), dim3(128), 0, st, comp, blocks, nblocks, lit);
 }
-static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k);
+static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, bool always);
 // which shared-table kernel a batch gets (zk_launch_fse); 0: none, the batch is small and every block takes a quad of lanes
 static int zk_fse_shared_kernel(uint32_t nblocks, const ZkKernelChoice &k, uint32_t frames)
 {
@@ -2671,12 +2685,12 @@ bool zk_entropy_fused_wanted(uint32_t nblocks, uint32_t n_own_tables, const ZkKe
     if (k.entropy == 2) return k.fse_shared == 0 || k.fse_shared == 2;
     return ZK_ENTROPY_FUSED_DEFAULT && zk_fse_shared_kernel(nblocks, k, frames) == 2;
 }
-void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, uint8_t *lit, const ZkKernelChoice &k)
+void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, uint8_t *lit, const ZkKernelChoice &k, bool rest_always)
 {
     hipLaunchKernelGGL(zk_k_entropy_frame, dim3((nblocks + ZK_FSEP_LANES - 1) / ZK_FSEP_LANES), dim3(4 * ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs, lit);
-    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k);
+    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k, rest_always);
 }
-void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, uint32_t frames)
+void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, uint32_t frames, bool rest_always)
 {
     if (!nblocks) return;
     const int own_kernel = k.fse_own;
@@ -2699,10 +2713,12 @@ void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_
     if (shared == 3) hipLaunchKernelGGL(zk_k_fse_sets, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
     else if (shared == 2) hipLaunchKernelGGL(zk_k_fse_predef_fed, dim3(wgs), dim3(2 * ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
     else hipLaunchKernelGGL(zk_k_fse_predef<ZkRevU>, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
-    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k);
+    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k, rest_always);
 }
 // The pass behind the shared-table kernel (zk_launch_fse, zk_launch_entropy): the blocks it has not marked done.
-static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k)
+// always: run it although no block of the batch defines a table -- blocks that repeat a loaded dictionary's tables define none, yet a workgroup
+// of the shared-table kernel may leave them to this pass (a block that mixes the dictionary's tables with predefined ones matches no neighbour)
+static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, bool always)
 {
     const int own_kernel = k.fse_own;
     // blocks with their own tables (every block is visited, the others return at once): a quad of lanes per block.
@@ -2711,7 +2727,7 @@ static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blo
     // blocks of ~10 k sequences: 4.13 ms; 56-block workgroups 4.41; one lane per block 4.57).  Beyond that, 56 blocks
     // per CU on four waves (32768 blocks: 20.6 ms with one lane per block, 13.2 with quads).
     // own_kernel: zk_engine_set_fse_kernel (1 = the lane-per-block kernel, 2 = quads in the large layout).
-    if (!n_own_tables) return;              // no block defines a table: everything was shared (predefined)
+    if (!n_own_tables && !always) return;   // no block defines a table: everything was shared (predefined)
     if (own_kernel == 1) { hipLaunchKernelGGL((zk_k_fse<ZkCells16, 56, 8>), dim3((nblocks + 55) / 56), dim3(512), 0, st, comp, blocks, nblocks, seqs); return; }
     // (every block the shared-table kernel has not marked done is taken, predefined tables or not.  n_own_tables counts the
     // DEFINING blocks: an archive of this engine's encoder has one per frame, its blocks were all shared, and the pass that
@@ -2723,13 +2739,14 @@ static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blo
 }
 void zk_launch_exec(hipStream_t st, const uint8_t *comp, const uint64_t *d_off, uint32_t first, uint32_t count,
                     const uint32_t *ids, const uint64_t *out_off, const ZkBlock *blocks, const ZkFrameBase *bases, ZkFrameInfo *infos, const ZkSeqP *seqs,
-                    const uint8_t *lit, uint8_t *dst, const uint8_t *prefix, uint64_t plen, const ZkKernelChoice &k, bool dense, uint64_t *progress)
+                    const uint8_t *lit, uint8_t *dst, const uint8_t *prefix, uint64_t plen, const ZkKernelChoice &k, bool dense, uint64_t *progress, const uint32_t *rep_init)
 {
+    const ZkRepInit rep0 = {{rep_init ? rep_init[0] : 1u, rep_init ? rep_init[1] : 4u, rep_init ? rep_init[2] : 8u}};
     // one workgroup per frame: the tile width trades bytes in flight per frame against workgroups per CU
     // (measured on 2 MiB frames: 2048 frames -> 256 lanes.  128 lanes run the kernel alone in 8.9 instead of 9.5 ms -- eight
     // 2-wave workgroups per CU hold all 2048 frames in one round -- but leave no room for the neighbouring batch: with two
     // batches in flight the step is 18.8 ms against 17.2.  1024 frames: 256 lanes 4.95 ms, 128 lanes 6.9; 512 -> 512, 128 -> 1024)
-#define ZK_EXEC_LAUNCH(TT, PP, CC) hipLaunchKernelGGL((zk_k_exec<TT, PP, CC>), dim3(count), dim3(TT), (TT) == 256 ? pad : 0, st, comp, d_off, first, ids, out_off, blocks, bases, infos, seqs, lit, dst, prefix, plen, progress)
+#define ZK_EXEC_LAUNCH(TT, PP, CC) hipLaunchKernelGGL((zk_k_exec<TT, PP, CC>), dim3(count), dim3(TT), (TT) == 256 ? pad : 0, st, comp, d_off, first, ids, out_off, blocks, bases, infos, seqs, lit, dst, prefix, plen, progress, rep0)
     // ... and what a frame's matches reach: dense sequence streams (fewer than 10 output bytes per sequence: libzstd from level 3 up, whose
     // window is the whole 2 MiB frame -- every far match a line from beyond the L2) run better with FEWER frames resident: 512-lane tiles
     // hold 512 frames' histories live instead of 1 280 (4 GiB of the reference's level-3 frames: executor 17.0 -> 15.6 ms, the step with
@@ -2773,7 +2790,7 @@ void zk_launch_exec_seg(hipStream_t st, const uint8_t *comp, const uint64_t *d_o
     else hipLaunchKernelGGL((zk_k_exec_fill_lds<1024>), dim3(count), dim3(1024), 0, st, d_off, first, ids, out_off, bases, infos, dst, sg.segs, sg.nsegs, sg.max_segs, sg.holes, sg.tilecnt, sg.segn, progress);
     // frames a segment gave up on (more hole records than its region holds): executed again, a workgroup per frame
     hipLaunchKernelGGL((zk_k_exec<256, false, 2, true>), dim3(count), dim3(256), 0, st, comp, d_off, first, ids, out_off, blocks, bases, infos, seqs, lit, dst,
-                       (const uint8_t *)nullptr, (uint64_t)0, (uint64_t *)nullptr);
+                       (const uint8_t *)nullptr, (uint64_t)0, (uint64_t *)nullptr, ZkRepInit{{1u, 4u, 8u}});
 }
 void zk_launch_xxh64(hipStream_t st, const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count,
                      ZkFrameInfo *infos, uint64_t *hashes, const ZkKernelChoice &k, const uint64_t *skip, uint32_t wide_from, bool beside)

@@ -64,6 +64,7 @@ enum : uint32_t {
     ZK_E_WINDOW_TOO_LARGE = 16,
     ZK_E_CORRUPTION = 20,
     ZK_E_CHECKSUM_WRONG = 22,
+    ZK_E_DICT_CORRUPTED = 30,
     ZK_E_DICT_WRONG = 32,
     ZK_E_DST_TOO_SMALL = 70,
     ZK_E_SRC_SIZE_WRONG = 72,
@@ -94,7 +95,10 @@ struct ZkFrameBase {            // exclusive prefix sums over frames
 };
 
 struct ZkBlock {                // one per block, contiguous per frame
-    uint64_t src;               // absolute offset (in the compressed buffer) of the block content
+    uint64_t src;               // absolute offset (in the compressed buffer) of the block content.  KEEP IT 64-BIT wherever a table-defining
+                                // block is read (blocks[huf_def], blocks[tab_def[i]]): a loaded dictionary's entry (zk_dict.h) lies outside the
+                                // compressed buffer, its src is the distance to it modulo 2^64 and comp + src wraps round to it.  Only a
+                                // batch's own blocks, which lie below 4 GiB of one call's buffer, may be narrowed (zk_k_fse's staging does)
     uint64_t lit_base;          // literal scratch offset (Huffman literals)
     uint64_t seq_base;          // sequence scratch index
     uint32_t bsize;             // Block_Size
@@ -671,8 +675,14 @@ ZK_HD uint32_t zk_parse_nseq(const uint8_t *p, uint32_t avail, uint32_t &nseq)
 // ---------------------------------------------------------------- frame walker
 // One lane walks one frame.  blocks == nullptr: count only.
 // comp/c_begin/c_end: the frame occupies comp[c_begin, c_end).  d_size: expected decompressed size.
+// dw: the dictionary the decoder has loaded (ZSTD_DCtx_loadDictionary), passed by value; on == 0: none.  A frame may name its ID, name none or
+// carry no Dictionary_ID field; with a formatted dictionary the Huffman tree and the three sequence tables "in force" at the
+// frame's first block are the dictionary's: def is the index of the block entry that describes them (zk_dict.h).  A raw-content
+// dictionary has ID 0 and no tables (def = ZK_DEF_NONE): it only lends its bytes to the executor.
+constexpr uint32_t ZK_DEF_NONE = 0xFFFFFFFFu;       // no table in force yet: Treeless literals / Repeat_Mode are corruption
+struct ZkDictWalk { uint32_t on = 0, id = 0, def = ZK_DEF_NONE; };
 ZK_HD void zk_walk_frame(const uint8_t *comp, uint64_t c_begin, uint64_t c_end, uint64_t d_size,
-                         uint32_t frame_idx, const ZkFrameBase *base, ZkBlock *blocks, ZkFrameInfo &fi)
+                         uint32_t frame_idx, const ZkFrameBase *base, ZkBlock *blocks, ZkFrameInfo &fi, ZkDictWalk dw = ZkDictWalk())
 {
     fi.n_blocks = 0; fi.n_seq = 0; fi.lit_bytes = 0; fi.status = ZK_OK;
     fi.checksum_flag = 0; fi.checksum = 0; fi.window = 0; fi.n_own_tables = 0; fi.fcs = ZK_SIZE_UNKNOWN;
@@ -695,7 +705,7 @@ ZK_HD void zk_walk_frame(const uint8_t *comp, uint64_t c_begin, uint64_t c_end, 
     if (p + dl + fl > csz) { fi.status = ZK_E_SRC_SIZE_WRONG; return; }
     uint32_t dict = 0;
     for (uint32_t i = 0; i < dl; i++) dict |= (uint32_t)f[p + i] << (8 * i);
-    if (dict) { fi.status = ZK_E_DICT_WRONG; return; }
+    if (dict && !(dw.on && dw.id == dict)) { fi.status = ZK_E_DICT_WRONG; return; }
     p += dl;
     uint64_t fcs = 0;
     for (uint32_t i = 0; i < fl; i++) fcs |= (uint64_t)f[p + i] << (8 * i);
@@ -714,7 +724,8 @@ ZK_HD void zk_walk_frame(const uint8_t *comp, uint64_t c_begin, uint64_t c_end, 
     uint32_t block_max = window < ZK_BLOCK_MAX ? (uint32_t)window : ZK_BLOCK_MAX;
 
     uint64_t blk = base ? base->block_base : 0, seqb = base ? base->seq_base : 0, litb = base ? base->lit_base : 0;
-    uint32_t huf_def = 0xFFFFFFFFu, tab_def[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    const uint32_t def0 = dw.on ? dw.def : ZK_DEF_NONE;
+    uint32_t huf_def = def0, tab_def[3] = {def0, def0, def0};
     uint64_t out_known = 0;                                 // regenerated bytes of raw/rle blocks (sanity bound)
     for (;;) {
         if (p + 3 > csz) { fi.status = ZK_E_SRC_SIZE_WRONG; return; }

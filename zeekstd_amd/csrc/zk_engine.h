@@ -46,6 +46,15 @@ struct zk_engine {
     // own calls through zk_engine_stage_prefix: owner + address + length name the staged bytes.
     zk_devbuf st_prefix;
     const void *st_prefix_owner = nullptr, *st_prefix_src = nullptr; uint64_t st_prefix_len = 0;
+    // the dictionary every decode call applies (zk_engine_set_dictionary; zk_dict.h): the engine's own device copy --
+    // [block entry | entropy section as a block's content | content] -- uploaded once
+    struct Dict {
+        bool on = false, tables = false;    // tables: a formatted dictionary
+        uint32_t id = 0, rep[3] = {1, 4, 8};
+        zk_devbuf buf;
+        const ZkBlock *d_tmpl = nullptr; const uint8_t *d_img = nullptr, *d_content = nullptr;
+        uint64_t content_len = 0;
+    } dict;
     struct zk_hostpipe *hp = nullptr;       // host-pointer pipeline (pinned staging, copy queues, worker threads): zk_engine_host.hip
     int host_threads = 0;                   // zk_engine_set_host_threads (0 = default)
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
@@ -97,6 +106,10 @@ int zk_dec_ctx_aux(zk_engine *e, int slot);             // the context's second 
 int zk_dec_ctx_ready(zk_engine *e, int slot);           // creates the context's queues / events on first use
 zk_dec_ctx zk_dec_context(zk_engine *e, int slot, void *stream);
 int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a);
+// does this call decode against the engine's dictionary?  (an explicit prefix overrides it, as ZSTD_DCtx_refPrefix does)
+inline bool zk_dict_applies(const zk_engine *e, const void *d_prefix) { return e->dict.on && !d_prefix; }
+// what the frame walk needs of it; nblocks: the batch's block count (0 for the counting pass, which writes no block entry)
+ZkWalkDict zk_dict_walk_args(const zk_engine *e, bool applies, uint64_t nblocks, bool fill);
 int zk_decode_finish(zk_engine *e, zk_dec_ctx &c);
 namespace zeekstd { class SeekTable; }
 struct zk_seek_table;

@@ -11,6 +11,7 @@
 #include "../../include/zeekstd_amd.h"
 #include "zk_engine.h"
 #include "zk_kernels.h"
+#include "zk_dict.h"
 
 #define ZK_HIP(call)                                                                                 \
     do {                                                                                             \
@@ -162,7 +163,7 @@ extern "C" void zk_engine_destroy(zk_engine *e)
     zk_hostpipe_destroy(e);
     if (e->enc_pin) (void)hipHostFree(e->enc_pin);
     for (auto &c : e->dctx) if (c.st) (void)hipStreamSynchronize(c.st);
-    zk_devbuf *bufs[] = {&e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc,
+    zk_devbuf *bufs[] = {&e->dict.buf, &e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc,
                          &e->enc_a, &e->enc_b, &e->enc_c, &e->enc_d, &e->enc_e, &e->enc_f, &e->enc_hist, &e->enc_seg, &e->enc_ldm, &e->enc_dense};
     for (zk_devbuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (e->h_words) (void)hipHostFree(e->h_words);
@@ -253,8 +254,25 @@ static bool zk_seg_wanted(const zk_engine *e, const zk_dec_args &a, uint32_t cou
 
 // Enqueue the whole decode on the context's queues.  Blocks the host once, for the block / sequence / literal totals
 // that size the scratch (40 bytes, after the two cheapest kernels); returns with the rest still running.
-int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a)
+ZkWalkDict zk_dict_walk_args(const zk_engine *e, bool applies, uint64_t nblocks, bool fill)
 {
+    ZkWalkDict wd;
+    if (!applies) return wd;
+    wd.on = 1; wd.id = e->dict.id;
+    if (e->dict.tables) {
+        wd.def = (uint32_t)nblocks;                         // (the counting pass only asks "is a table in force": any index will do)
+        if (fill) { wd.tmpl = e->dict.d_tmpl; wd.img = e->dict.d_img; }
+    }
+    return wd;
+}
+
+int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a_in)
+{
+    // the engine's dictionary: its content is the prefix of every frame, its repeat offsets their first history, its tables the
+    // ones in force at their first block (ZSTD_DCtx_loadDictionary)
+    const bool with_dict = zk_dict_applies(e, a_in.d_prefix);
+    zk_dec_args a = a_in;
+    if (with_dict && e->dict.content_len) { a.d_prefix = e->dict.d_content; a.prefix_len = e->dict.content_len; }
     // history positions are 32-bit words biased by 2^30 (zk_device.h): a frame plus its prefix must fit below that
     if (a.d_prefix && a.prefix_len > ZK_MAX_PREFIX) return -(int)ZK_E_WINDOW_TOO_LARGE;
     hipStream_t st = c.st;
@@ -270,13 +288,15 @@ int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a)
     uint64_t *words = (uint64_t *)c.words.p;          // [0..2] totals, [3] first error
 
     zk_profile_begin(e);
-    { zk_kernel_timer t(e, ZK_K_WALK_COUNT, st); zk_launch_walk(st, comp, a.comp_size, c_off, d_off, first, count, a.ids, a.out_off, a.dst_cap, nullptr, nullptr, infos); }
+    { zk_kernel_timer t(e, ZK_K_WALK_COUNT, st); zk_launch_walk(st, comp, a.comp_size, c_off, d_off, first, count, a.ids, a.out_off, a.dst_cap, nullptr, nullptr, infos, zk_dict_walk_args(e, with_dict, 0, false)); }
     { zk_kernel_timer t(e, ZK_K_SCAN, st); zk_launch_scan(st, infos, count, bases, words, d_off, first, a.out_off); }
     ZK_HIP(hipMemcpyAsync(c.h_words, words, 9 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
     const uint64_t nblocks = c.h_words[0], nseq = c.h_words[1], nlit = c.h_words[2];
     const bool verify = a.verify && c.h_words[8] != 0;    // (a batch without a Content_Checksum: zeekstd's library default, encode.rs:163-167 -- no checksum kernel is launched)
     const uint32_t n_own = (uint32_t)c.h_words[4];        // blocks that need per-block sequence tables
+    // the pass behind the shared-table kernels has to run whenever a dictionary lends tables (zk_launch_fse_rest)
+    const bool rest_always = with_dict && e->dict.tables;
     const bool dense = nseq * 10 > c.h_words[5];          // fewer than 10 output bytes per sequence (zk_launch_exec)
     const uint64_t out_bytes = c.h_words[5], max_frame = c.h_words[7];
     if (nblocks > 0xFFFFFFF0ull) return -(int)ZK_E_GENERIC;
@@ -320,17 +340,17 @@ int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a)
         ZK_HIP(hipMemsetAsync(prog, 0, (size_t)count * sizeof(uint64_t), st));
     }
     ZK_HIP(hipMemsetAsync(words + 6, 0, sizeof(uint64_t), st));
-    { zk_kernel_timer t(e, ZK_K_WALK_FILL, st); zk_launch_walk(st, comp, a.comp_size, c_off, d_off, first, count, a.ids, a.out_off, a.dst_cap, bases, blocks, infos); }
+    { zk_kernel_timer t(e, ZK_K_WALK_FILL, st); zk_launch_walk(st, comp, a.comp_size, c_off, d_off, first, count, a.ids, a.out_off, a.dst_cap, bases, blocks, infos, zk_dict_walk_args(e, with_dict, nblocks, true)); }
     // literals (huf) and sequences (fse) of a block are independent: the two kernels run side by side on two queues;
     // with per-kernel timing on they are serialised instead
     // ... or, where the sequences would get zk_k_fse_predef_fed, both in one kernel whose workgroups each bring a Huffman half and a
     // sequence half (zk_k_entropy_frame: no second queue, no events)
     const bool fused = !e->profiling && !a.single_queue && zk_entropy_fused_wanted((uint32_t)nblocks, n_own, e->choice, count);
     e->dctx[c.slot].fused = fused;
-    if (fused) zk_launch_entropy(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, lit, e->choice);
+    if (fused) zk_launch_entropy(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, lit, e->choice, rest_always);
     else if (e->profiling || a.single_queue) {
         { zk_kernel_timer t(e, ZK_K_HUF, st); zk_launch_huf(st, comp, blocks, (uint32_t)nblocks, lit); }
-        { zk_kernel_timer t(e, ZK_K_FSE, st); zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count); }
+        { zk_kernel_timer t(e, ZK_K_FSE, st); zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count, rest_always); }
     } else {
         if ((rc = zk_dec_ctx_aux(e, c.slot))) return rc;
         zk_engine::DecCtx &x = e->dctx[c.slot];
@@ -338,7 +358,7 @@ int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a)
         ZK_HIP(hipStreamWaitEvent(x.aux, x.ev_fork, 0));
         zk_launch_huf(x.aux, comp, blocks, (uint32_t)nblocks, lit);
         ZK_HIP(hipEventRecord(x.ev_join, x.aux));
-        zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count);
+        zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count, rest_always);
         ZK_HIP(hipStreamWaitEvent(st, x.ev_join, 0));
     }
     const uint64_t *x_off = a.out_off ? a.out_off : d_off;   // packed indexed output: out_off (count + 1 prefix sums) doubles as the d_off of the checksum kernels
@@ -349,7 +369,7 @@ int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a)
         ZK_HIP(hipStreamWaitEvent(x.aux, x.ev_fork, 0));
     }
     if (seg) { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec_seg(st, comp, d_off, first, count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, (uint8_t *)a.d_dst, sgs, kc, dense, prog); }
-    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, first, count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, (uint8_t *)a.d_dst, (const uint8_t *)a.d_prefix, a.d_prefix ? a.prefix_len : 0, kc, dense, prog); }
+    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, first, count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, (uint8_t *)a.d_dst, (const uint8_t *)a.d_prefix, a.d_prefix ? a.prefix_len : 0, kc, dense, prog, with_dict ? e->dict.rep : nullptr); }
     if (a.mark_exec) ZK_HIP(hipEventRecord(c.ev_exec, st));
     if (follow) {
         // enqueued BEHIND the executor's launch: were the two queues ever served one after the other, the checksum waves would find
@@ -450,6 +470,58 @@ extern "C" int zk_decode_frame_list_dev(zk_engine *e, const void *d_comp, uint64
     return zk_decode_impl(e, a, stream);
 }
 
+// ---------------------------------------------------------------------------------------------- dictionaries
+// zk_dict: a dictionary parsed and validated on the host (zk_dict.h; no GPU involved).  zk_engine_set_dictionary uploads it once; every
+// decode call of the engine then follows ZSTD_DCtx_loadDictionary (zk_decode_enqueue, zk_frame_content_sizes_dev).
+extern "C" int zk_dict_create(const uint8_t *bytes, size_t len, zk_dict **out)
+{
+    if (!out || (len && !bytes)) return ZK_ERR_ARGUMENT;
+    *out = nullptr;
+    ZkDictLayout L;
+    const uint32_t st = zk_dict_parse(bytes, len, L);
+    if (st != ZK_OK) return -(int)st;
+    if (len - L.content_off > ZK_MAX_PREFIX) return -(int)ZK_E_WINDOW_TOO_LARGE;     // the content is a prefix (zk_decode_frames_prefix)
+    zk_dict *d = new zk_dict();
+    d->bytes.assign(bytes, bytes + len);
+    d->L = L;
+    *out = d;
+    return 0;
+}
+extern "C" void zk_dict_free(zk_dict *d) { delete d; }
+extern "C" uint32_t zk_dict_id(const zk_dict *d) { return d ? d->L.id : 0; }
+extern "C" size_t zk_dict_content_offset(const zk_dict *d) { return d ? d->L.content_off : 0; }
+
+extern "C" int zk_engine_set_dictionary(zk_engine *e, const zk_dict *d)
+{
+    if (!e) return ZK_ERR_ARGUMENT;
+    if (e->slot_busy[0] || e->slot_busy[1]) return ZK_ERR_ARGUMENT;     // a submitted batch decodes against the dictionary it was submitted with
+    ZK_HIP(hipSetDevice(e->device));
+    for (auto &c : e->dctx) if (c.st) ZK_HIP(hipStreamSynchronize(c.st));
+    e->dict.on = false;
+    if (!d || d->bytes.empty()) return 0;
+    std::vector<uint8_t> img;
+    ZkBlock blk;
+    memset(&blk, 0, sizeof blk);
+    if (d->L.formatted) zk_dict_block(d->bytes.data(), d->L, img, blk);
+    // [block entry | its content, padded to 64 bytes | the dictionary's content | 64 readable bytes]
+    const size_t img_at = 128, img_room = (img.size() + 63) & ~(size_t)63, content_at = img_at + img_room;
+    const size_t content_len = d->bytes.size() - d->L.content_off;
+    int rc;
+    if ((rc = zk_devbuf_reserve(e, e->dict.buf, content_at + content_len + 64))) return rc;
+    std::vector<uint8_t> h(content_at + content_len + 64, 0);
+    memcpy(h.data(), &blk, sizeof blk);
+    if (!img.empty()) memcpy(h.data() + img_at, img.data(), img.size());
+    if (content_len) memcpy(h.data() + content_at, d->bytes.data() + d->L.content_off, content_len);
+    ZK_HIP(hipMemcpy(e->dict.buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    const uint8_t *base = (const uint8_t *)e->dict.buf.p;
+    e->dict.d_tmpl = (const ZkBlock *)base; e->dict.d_img = base + img_at; e->dict.d_content = base + content_at;
+    e->dict.content_len = content_len;
+    e->dict.tables = d->L.formatted; e->dict.id = d->L.id;
+    e->dict.rep[0] = d->L.rep[0]; e->dict.rep[1] = d->L.rep[1]; e->dict.rep[2] = d->L.rep[2];
+    e->dict.on = true;
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- frame sizes nobody knows yet
 // What libzstd's streaming decoder needs no table for -- how many bytes a frame decodes to -- this engine is told by the seek table
 // (lib/src/seek_table.rs:750).  A host that holds frames WITHOUT their entries (the Level-C shim under an unmodified zeekstd hands
@@ -476,7 +548,8 @@ extern "C" int zk_frame_content_sizes_dev(zk_engine *e, const void *d_comp, uint
     ZkFrameInfo *infos = (ZkFrameInfo *)c.infos.p;
     ZkFrameBase *bases = (ZkFrameBase *)c.bases.p;
     uint64_t *words = (uint64_t *)c.words.p;
-    zk_launch_walk(st, comp, comp_size, c_off, nullptr, first, count, nullptr, nullptr, 0, nullptr, nullptr, infos);
+    const bool with_dict = zk_dict_applies(e, nullptr);
+    zk_launch_walk(st, comp, comp_size, c_off, nullptr, first, count, nullptr, nullptr, 0, nullptr, nullptr, infos, zk_dict_walk_args(e, with_dict, 0, false));
     zk_launch_scan(st, infos, count, bases, words, nullptr, first, nullptr);
     ZK_HIP(hipMemcpyAsync(c.h_words, words, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
@@ -485,8 +558,8 @@ extern "C" int zk_frame_content_sizes_dev(zk_engine *e, const void *d_comp, uint
     if ((rc = zk_devbuf_reserve(e, c.blocks, (size_t)(nblocks + 1) * sizeof(ZkBlock)))) return rc;
     if ((rc = zk_devbuf_reserve(e, c.seqs, (size_t)(nseq + 1) * sizeof(ZkSeqP)))) return rc;
     ZkBlock *blocks = (ZkBlock *)c.blocks.p;
-    zk_launch_walk(st, comp, comp_size, c_off, nullptr, first, count, nullptr, nullptr, 0, bases, blocks, infos);
-    zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, (uint32_t)c.h_words[4], (ZkSeqP *)c.seqs.p, e->choice, count);
+    zk_launch_walk(st, comp, comp_size, c_off, nullptr, first, count, nullptr, nullptr, 0, bases, blocks, infos, zk_dict_walk_args(e, with_dict, nblocks, true));
+    zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, (uint32_t)c.h_words[4], (ZkSeqP *)c.seqs.p, e->choice, count, with_dict && e->dict.tables);
     zk_launch_frame_sizes(st, infos, bases, blocks, count, (uint64_t *)d_sizes, (int32_t *)d_frame_status);
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());

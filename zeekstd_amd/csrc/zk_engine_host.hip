@@ -567,7 +567,8 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
     for (auto &ck : chunks) if (ck.c1 - ck.c0 > max_c) max_c = ck.c1 - ck.c0;
     // a small request (a seek) is staged through one small pinned buffer by this thread: no rings, no hand-over
     const bool small = nchunks == 1 && total_d <= (4u << 20) && max_c <= (4u << 20);
-    if (small && count <= 64 && !e->profiling && e->choice.small_path != 1) {
+    // (a batch that decodes against the engine's dictionary takes the general pipeline: the small path's one-kernel walk knows none)
+    if (small && count <= 64 && !e->profiling && e->choice.small_path != 1 && !zk_dict_applies(e, d_prefix)) {
         bool fallback = false;
         rc = zk_decode_small(e, hp, src, c_off, d_off, first, count, d_prefix, prefix_len, dst, dst_pinned, verify, frame_status, n_ok, &fallback);
         if (!fallback) return rc;

@@ -24,20 +24,28 @@ struct ZkKernelChoice {
 // scratch of the segmented executor (zk_engine.hip sizes it; zk_device.h: zk_seg_region)
 struct ZkSegScratch { ZkSeg *segs; uint32_t *nsegs, *segn; ZkHole *holes; uint32_t *tilecnt; uint32_t max_segs, seg_bytes; };
 
+// A loaded dictionary as the frame walk sees it (zk_dict.h).  on: one is loaded; id: its Dictionary_ID (0: raw content); def: the index of the
+// block entry that describes its tables = the batch's block count (ZK_DEF_NONE: raw content, no tables); tmpl / img (device memory): that
+// entry and the "block content" it describes -- the fill pass writes the entry to blocks[def].
+struct ZkWalkDict { uint32_t on = 0, id = 0, def = ZK_DEF_NONE; const ZkBlock *tmpl = nullptr; const uint8_t *img = nullptr; };
+struct ZkRepInit { uint32_t r[3]; };                     // the repeat offsets a frame starts with (zk_k_exec with a prefix)
 void zk_launch_walk(hipStream_t st, const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off, const uint64_t *d_off, uint32_t first,
-                    uint32_t count, const uint32_t *ids, const uint64_t *out_off, uint64_t dst_cap, const ZkFrameBase *bases, ZkBlock *blocks, ZkFrameInfo *infos);
+                    uint32_t count, const uint32_t *ids, const uint64_t *out_off, uint64_t dst_cap, const ZkFrameBase *bases, ZkBlock *blocks, ZkFrameInfo *infos,
+                    const ZkWalkDict &wd = ZkWalkDict());
 void zk_launch_frame_sizes(hipStream_t st, const ZkFrameInfo *infos, const ZkFrameBase *bases, const ZkBlock *blocks, uint32_t count, uint64_t *sizes, int32_t *status_out);
 void zk_launch_scan(hipStream_t st, const ZkFrameInfo *infos, uint32_t count, ZkFrameBase *bases, uint64_t *totals, const uint64_t *d_off, uint32_t first, const uint64_t *out_off);
 void zk_launch_huf(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint8_t *lit);
-void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, uint32_t frames = 0);
+void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, uint32_t frames = 0,
+                   bool rest_always = false);   // rest_always: the pass behind the shared-table kernel runs although n_own_tables is 0 (a dictionary's tables)
 // zk_k_entropy_frame in place of zk_launch_huf || zk_launch_fse: whether a batch gets it, and the launch (with the pass for the blocks it leaves)
 constexpr bool ZK_ENTROPY_FUSED_DEFAULT = true;
 bool zk_entropy_fused_wanted(uint32_t nblocks, uint32_t n_own_tables, const ZkKernelChoice &k, uint32_t frames);
-void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, uint8_t *lit, const ZkKernelChoice &k);
+void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, uint8_t *lit, const ZkKernelChoice &k, bool rest_always = false);
 void zk_launch_exec(hipStream_t st, const uint8_t *comp, const uint64_t *d_off, uint32_t first, uint32_t count,
                     const uint32_t *ids, const uint64_t *out_off, const ZkBlock *blocks, const ZkFrameBase *bases, ZkFrameInfo *infos, const ZkSeqP *seqs,
                     const uint8_t *lit, uint8_t *dst, const uint8_t *prefix, uint64_t plen, const ZkKernelChoice &k, bool dense = false,
-                    uint64_t *progress = nullptr);      // progress: one word per frame for zk_launch_xxh64_follow (zk_decode.hip: zk_publish)
+                    uint64_t *progress = nullptr,       // progress: one word per frame for zk_launch_xxh64_follow (zk_decode.hip: zk_publish)
+                    const uint32_t *rep_init = nullptr); // with a prefix: the three repeat offsets every frame starts with (a dictionary's; nullptr = 1 / 4 / 8)
 void zk_launch_exec_seg(hipStream_t st, const uint8_t *comp, const uint64_t *d_off, uint32_t first, uint32_t count,
                         const uint32_t *ids, const uint64_t *out_off, const ZkBlock *blocks, const ZkFrameBase *bases, ZkFrameInfo *infos, const ZkSeqP *seqs,
                         const uint8_t *lit, uint8_t *dst, const ZkSegScratch &sg, const ZkKernelChoice &k, bool dense, uint64_t *progress = nullptr);

@@ -18,6 +18,32 @@ def _u64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
 
 
+class Dictionary:
+    """A zstd dictionary for decoding (zk_dict_create): parsed and validated on the host, no GPU needed.  Bytes that begin with the
+    dictionary magic are a formatted dictionary (ZkError -30 when it is damaged), anything else is raw content (id 0)."""
+
+    def __init__(self, data: bytes):
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        h = C.c_void_p()
+        rc = lib.zk_dict_create(buf.ctypes.data if buf.size else None, buf.size, C.byref(h))
+        if rc != 0:
+            raise ZkError(rc)
+        self._h = h
+
+    @property
+    def id(self) -> int:
+        return int(lib.zk_dict_id(self._h))
+
+    @property
+    def content_offset(self) -> int:
+        return int(lib.zk_dict_content_offset(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib.zk_dict_free(self._h)
+            self._h = None
+
+
 class Engine:
     """Owns one GPU's scratch + stream. One thread at a time (like a libzstd context)."""
 
@@ -42,6 +68,12 @@ class Engine:
     @property
     def device_name(self) -> str:
         return lib.zk_engine_device_name(self._h).decode()
+
+    def set_dictionary(self, d):
+        """Every later decode call of this engine decodes against Dictionary d (zk_engine_set_dictionary); None = none."""
+        rc = lib.zk_engine_set_dictionary(self._h, d._h if d is not None else None)
+        if rc != 0:
+            self._raise(rc)
 
     def set_profiling(self, on: bool):
         rc = lib.zk_engine_set_profiling(self._h, int(on))
