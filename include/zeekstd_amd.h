@@ -103,7 +103,7 @@ enum {
     ZK_CHOICE_EXEC_RESIDENT = 9,  /* zk_k_exec with 256-lane tiles: at most this many workgroups per CU (4 or 5; the launch asks for LDS it does not use) */
     ZK_CHOICE_EXEC_SEG = 10,      /* the executor in segments, several workgroups per frame (zk_k_seg_prep / zk_k_exec_seg / zk_k_exec_fill): 1 never, 2 always
                                      (decodes without a prefix); 0 = by batch shape */
-    ZK_CHOICE_SEG_KIB = 11,       /* ... output KiB per segment (1..128; 0 = 128) */
+    ZK_CHOICE_SEG_KIB = 11,       /* ... output KiB per segment (1..128; 0 = 128, or 4 for short frames on the host-pointer small path) */
     ZK_CHOICE_SEG_FILL = 12,      /* ... its fill pass: 1 zk_k_exec_fill<1024> (rounds through memory), 2 zk_k_exec_fill<256>, 3 zk_k_exec_fill_lds (holes in LDS); 0 by batch size */
     ZK_CHOICE_ENTROPY = 13,       /* literals and sequences of a device-pointer batch: 1 = zk_k_huf beside the sequence kernels on two queues, 2 = one kernel
                                    * (zk_k_entropy_frame) for every batch that qualifies -- no frame with more than one set of own tables -- whatever its

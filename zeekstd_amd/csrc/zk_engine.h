@@ -5,6 +5,7 @@
 #include <string>
 #include "zk_enc_device.h"
 #include "zk_kernels.h"
+#include "zk_dec_plan.h"
 
 enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_EXEC, ZK_K_XXH64, ZK_K_STATUS,
        ZK_K_ENC_MATCH, ZK_K_ENC_ENTROPY, ZK_K_ENC_COMPACT, ZK_K_ENC_XXH64, ZK_K_ENC_FSE_BUILD, ZK_K_ENC_DENSE,
@@ -12,9 +13,6 @@ enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };
-// the checksums of a verified batch beside its executor (zk_k_xxh64_follow) or behind it: zk_follow_wanted (zk_engine.hip);
-// ZK_CHOICE_XXH64 = 4 asks for "beside" whatever the batch looks like, 1..3 for one of the passes behind the executor
-constexpr uint64_t ZK_FOLLOW_MIN_FRAME_BYTES = 512u << 10;
 
 struct zk_engine {
     int device = 0;
@@ -86,12 +84,8 @@ struct zk_engine {
 
 int zk_devbuf_reserve(zk_engine *e, zk_devbuf &b, size_t bytes);
 
-// ---- decode plumbing shared by zk_engine.hip (device-pointer entry points) and zk_engine_host.hip (host pipeline)
-struct zk_dec_ctx {
-    int slot; hipStream_t st; hipEvent_t ev_exec;
-    zk_devbuf &infos, &bases, &words, &blocks, &seqs, &lit;
-    uint64_t *h_words;
-};
+// ---- decode plumbing shared by zk_engine.hip (device-pointer entry points), zk_engine_host.hip (host pipeline, small path) and
+// zk_engine_ranges.hip.  Every stage takes the context and the queue to run on: zk_dec_stream.
 struct zk_dec_args {
     const void *d_comp; uint64_t comp_size; const void *d_c_off, *d_d_off; uint32_t first, count;
     const uint32_t *ids; const uint64_t *out_off;       // frame list (device arrays, both or neither)
@@ -101,16 +95,34 @@ struct zk_dec_args {
     bool single_queue = false;                          // huf and fse on the context's main queue (the host pipeline overlaps whole chunks instead)
     bool mark_exec = false;                             // record the context's ev_exec behind the executor (output bytes final, checksums pending)
 };
-bool zk_follow_wanted(const zk_engine *e, uint32_t count, uint64_t out_bytes, bool alone);
-int zk_dec_ctx_aux(zk_engine *e, int slot);             // the context's second queue + fork / join events, on first use
+int zk_dec_ctx_aux(zk_engine *e, zk_engine::DecCtx &c); // the context's second queue + fork / join events, on first use
 int zk_dec_ctx_ready(zk_engine *e, int slot);           // creates the context's queues / events on first use
-zk_dec_ctx zk_dec_context(zk_engine *e, int slot, void *stream);
-int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a);
+// the queue a decode on context c runs on: the caller's for context 0 when one is given, the context's own otherwise
+inline hipStream_t zk_dec_stream(zk_engine *e, zk_engine::DecCtx &c, void *stream) { return &c == &e->dctx[0] && stream ? (hipStream_t)stream : c.st; }
+inline ZkDecShape zk_dec_shape(const zk_engine *e, uint32_t count, uint64_t out_bytes, uint64_t max_frame, uint64_t nblocks, bool has_prefix, bool alone)
+{
+    return ZkDecShape{e->choice.xxh, e->choice.exec_seg, e->choice.seg_kib, e->profiling, count, out_bytes, max_frame, nblocks, has_prefix, alone, false};
+}
+int zk_decode_enqueue(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a);
+int zk_decode_finish(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st);
+// the stages of a decode (zk_engine.hip), in the order zk_decode_enqueue runs them; a.d_comp ... a.dst_cap name the frames
+int zk_dec_frame_tables(zk_engine *e, zk_engine::DecCtx &c, uint32_t count);            // infos / bases / words for `count` frames
+// counting walk + scan; blocks until the first `nwords` of the ZK_SCAN_* words are in c.h_words
+int zk_dec_count_pass(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, bool with_dict, uint32_t nwords);
+int zk_dec_block_scratch(zk_engine *e, zk_engine::DecCtx &c, uint64_t nblocks, uint64_t nseq);    // blocks / seqs
+// the frame walk: the counting pass's (fill = false: no block entries yet), the filling one
+void zk_dec_walk(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, bool with_dict, uint64_t nblocks, bool fill);
+// scratch of the executor in segments; nblocks: the batch's block count or a bound of it
+int zk_dec_seg_scratch(zk_engine *e, zk_engine::DecCtx &c, uint32_t count, const ZkSegPlan &sp, uint64_t out_bytes, uint64_t nblocks, ZkSegScratch &sgs);
+// the checksums beside the executor: its progress words (cleared on st) and the context's second queue
+int zk_dec_follow_prepare(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, uint32_t count, uint64_t **prog);
+int zk_dec_fork(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st);     // the second queue goes on from where st is now
+// the executor (sgs: in segments; kc: its choice), ev_exec when a.mark_exec, then the checksums: zk_k_xxh64_follow on the second queue and
+// what it left when `prog` (zk_dec_follow_prepare + zk_dec_fork came first), the plain pass when a.verify, else none
+int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, const ZkSegScratch *sgs, const ZkKernelChoice &kc,
+                          bool dense, uint64_t *prog, const uint32_t *rep_init);
 // does this call decode against the engine's dictionary?  (an explicit prefix overrides it, as ZSTD_DCtx_refPrefix does)
 inline bool zk_dict_applies(const zk_engine *e, const void *d_prefix) { return e->dict.on && !d_prefix; }
-// what the frame walk needs of it; nblocks: the batch's block count (0 for the counting pass, which writes no block entry)
-ZkWalkDict zk_dict_walk_args(const zk_engine *e, bool applies, uint64_t nblocks, bool fill);
-int zk_decode_finish(zk_engine *e, zk_dec_ctx &c);
 namespace zeekstd { class SeekTable; }
 struct zk_seek_table;
 zk_seek_table *zk_seek_table_from_cpp(const zeekstd::SeekTable *t);
@@ -157,6 +169,12 @@ struct zk_kernel_timer {
         if (e->profiling) { (void)hipEventRecord(e->ev_start[k], st); e->ev_used[k] = true; }
     }
     ~zk_kernel_timer() { if (e->profiling) (void)hipEventRecord(e->ev_stop[k], st); }
+};
+// per-kernel events describe one synchronous batch: everything else runs with profiling off for a scope
+struct zk_profiling_off {
+    zk_engine *e; bool was;
+    explicit zk_profiling_off(zk_engine *e_, bool off = true) : e(e_), was(e_->profiling) { if (off) e->profiling = false; }
+    ~zk_profiling_off() { e->profiling = was; }
 };
 void zk_profile_begin(zk_engine *e);
 void zk_profile_collect(zk_engine *e);

@@ -204,57 +204,17 @@ int zk_dec_ctx_ready(zk_engine *e, int slot)
 }
 // the second queue of a context (huf || fse of one batch) exists only once a batch asked for it: the host pipeline overlaps
 // whole chunks on one queue per context, and every stream the process owns competes for the runtime's few hardware queues
-int zk_dec_ctx_aux(zk_engine *e, int slot)
+int zk_dec_ctx_aux(zk_engine *e, zk_engine::DecCtx &c)
 {
-    zk_engine::DecCtx &c = e->dctx[slot];
     if (c.aux) return 0;
     ZK_HIP(hipStreamCreateWithFlags(&c.aux, hipStreamNonBlocking));
     ZK_HIP(hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming));
     ZK_HIP(hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming));
     return 0;
 }
-zk_dec_ctx zk_dec_context(zk_engine *e, int slot, void *stream)
-{
-    zk_engine::DecCtx &c = e->dctx[slot];
-    return zk_dec_ctx{slot, slot == 0 && stream ? (hipStream_t)stream : c.st, c.ev_exec, c.infos, c.bases, c.words, c.blocks, c.seqs, c.lit, c.h_words};
-}
 
-// Where the checksums of a verified batch run: beside the executor (zk_k_xxh64_follow) or behind it.  Measured on 16 / 128 / 512 /
-// 2048 frames of 2 MiB (profiles/r04_follow_by_batch_size.txt; ms one batch at a time | two in flight; behind = the better of
-// the two passes behind the executor):   16: 4.27 -> 3.50 | 2.19 -> 1.91     128: 5.20 -> 5.77 | 3.03 -> 3.07
-//                                       512: 6.48 -> 6.76 | 5.32 -> 5.13    2048: 16.7 -> 15.7 | 14.56 -> 14.49 (at four executor
-// workgroups per CU; five, the in-flight default, and a checksum wave do not fit a SIMD).  A few frames leave most CUs to the checksum
-// waves; a batch that fills the device alone trades 2.7 ms of an idle device for 1.7 ms of the executor; in between a frame IS a
-// workgroup and the slowest one -- the one that shares its SIMD -- ends the kernel.  Frames of less than 512 KiB are short chains.
-bool zk_follow_wanted(const zk_engine *e, uint32_t count, uint64_t out_bytes, bool alone)
-{
-    if (e->profiling) return false;                         // (per-kernel timing serialises the kernels)
-    if (e->choice.xxh) return e->choice.xxh == 4;
-    if (out_bytes < (uint64_t)count * ZK_FOLLOW_MIN_FRAME_BYTES) return false;
-    if (count <= 64) return true;
-    return alone ? count >= 1024 : count < 1024;
-}
-
-// Several workgroups per frame (zk_k_exec_seg + zk_k_exec_fill) instead of one (zk_k_exec)?  Never with a prefix (history below the frame's
-// first byte is the serial kernel's), never when a frame could have more segments than a grid has rows.
-static bool zk_seg_wanted(const zk_engine *e, const zk_dec_args &a, uint32_t count, uint64_t out_bytes, uint64_t max_frame, uint64_t nblocks, bool follow)
-{
-    if (a.d_prefix || e->choice.exec_seg == 1 || !count || !nblocks) return false;
-    const uint32_t seg_bytes = e->choice.seg_kib ? (uint32_t)e->choice.seg_kib << 10 : ZK_SEG_BYTES;
-    if (2 * ((max_frame + seg_bytes - 1) / seg_bytes) + 1 > 65535) return false;
-    if (e->choice.exec_seg == 2) return true;
-    // by batch shape: a handful of long frames, where a frame as ONE workgroup leaves the device idle (2 MiB frames, HBM-resident,
-    // unverified, ms: 1 / 5 / 16 / 32 frames 2.58 / 2.60 / 2.62 / 2.65 -> 1.79 / 1.83 / 1.85 / 2.39; 64 frames 2.80 -> 2.88: profiles/r06_seg_probe.txt).
-    // Not where the checksums run beside the executor: a frame's four XXH64 chains (1.7-2.3 ms per 2 MiB, whoever runs them) then end
-    // the decode, not the executor (verified, 16 frames: 3.52 ms either way).
-    // (r6, with a wave per frame behind the progress words -- zk_k_xxh64_follow1 -- verified, ms, frame executor | segments: 1 frame 2.94 | 3.01,
-    //  5: 3.05 | 3.14, 16: 3.08 | 3.31, 32: 3.69 | 3.33)
-    return (!follow || count > 16) && count <= 32 && out_bytes >= (uint64_t)count * (4u * ZK_SEG_BYTES);
-}
-
-// Enqueue the whole decode on the context's queues.  Blocks the host once, for the block / sequence / literal totals
-// that size the scratch (40 bytes, after the two cheapest kernels); returns with the rest still running.
-ZkWalkDict zk_dict_walk_args(const zk_engine *e, bool applies, uint64_t nblocks, bool fill)
+// what the frame walk needs of the dictionary; nblocks: the batch's block count (0 for the counting pass, which writes no block entry)
+static ZkWalkDict zk_dict_walk_args(const zk_engine *e, bool applies, uint64_t nblocks, bool fill)
 {
     ZkWalkDict wd;
     if (!applies) return wd;
@@ -266,7 +226,94 @@ ZkWalkDict zk_dict_walk_args(const zk_engine *e, bool applies, uint64_t nblocks,
     return wd;
 }
 
-int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a_in)
+// ---- the stages (zk_engine.h)
+int zk_dec_frame_tables(zk_engine *e, zk_engine::DecCtx &c, uint32_t count)
+{
+    int rc;
+    if ((rc = zk_devbuf_reserve(e, c.infos, (size_t)count * sizeof(ZkFrameInfo)))) return rc;
+    if ((rc = zk_devbuf_reserve(e, c.bases, (size_t)count * sizeof(ZkFrameBase)))) return rc;
+    return zk_devbuf_reserve(e, c.words, 16 * sizeof(uint64_t));       // [0..2] totals, [3] first error (zk_dec_plan.h)
+}
+void zk_dec_walk(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, bool with_dict, uint64_t nblocks, bool fill)
+{
+    zk_kernel_timer t(e, fill ? ZK_K_WALK_FILL : ZK_K_WALK_COUNT, st);
+    zk_launch_walk(st, (const uint8_t *)a.d_comp, a.comp_size, (const uint64_t *)a.d_c_off, (const uint64_t *)a.d_d_off, a.first, a.count, a.ids, a.out_off, a.dst_cap,
+                   fill ? (const ZkFrameBase *)c.bases.p : nullptr, fill ? (ZkBlock *)c.blocks.p : nullptr, (ZkFrameInfo *)c.infos.p, zk_dict_walk_args(e, with_dict, nblocks, fill));
+}
+int zk_dec_count_pass(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, bool with_dict, uint32_t nwords)
+{
+    zk_dec_walk(e, c, st, a, with_dict, 0, false);
+    { zk_kernel_timer t(e, ZK_K_SCAN, st); zk_launch_scan(st, (const ZkFrameInfo *)c.infos.p, a.count, (ZkFrameBase *)c.bases.p, (uint64_t *)c.words.p, (const uint64_t *)a.d_d_off, a.first, a.out_off); }
+    ZK_HIP(hipMemcpyAsync(c.h_words, c.words.p, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+int zk_dec_block_scratch(zk_engine *e, zk_engine::DecCtx &c, uint64_t nblocks, uint64_t nseq)
+{
+    if (nblocks > 0xFFFFFFF0ull) return -(int)ZK_E_GENERIC;
+    int rc;
+    if ((rc = zk_devbuf_reserve(e, c.blocks, (size_t)(nblocks + 1) * sizeof(ZkBlock)))) return rc;
+    return zk_devbuf_reserve(e, c.seqs, (size_t)(nseq + 1) * sizeof(ZkSeqP));
+}
+int zk_dec_seg_scratch(zk_engine *e, zk_engine::DecCtx &c, uint32_t count, const ZkSegPlan &sp, uint64_t out_bytes, uint64_t nblocks, ZkSegScratch &sgs)
+{
+    int rc;
+    const uint64_t nsg = (uint64_t)count * sp.max_segs;
+    if ((rc = zk_devbuf_reserve(e, c.seg_tab, (size_t)nsg * sizeof(ZkSeg)))) return rc;
+    if ((rc = zk_devbuf_reserve(e, c.seg_cnt, (size_t)(nsg + count) * sizeof(uint32_t)))) return rc;
+    if ((rc = zk_devbuf_reserve(e, c.seg_holes, (size_t)((out_bytes >> 2) + 16 * nsg + 16) * sizeof(ZkHole)))) return rc;
+    if ((rc = zk_devbuf_reserve(e, c.seg_tiles, (size_t)((out_bytes >> 10) + 2 * nblocks + 8 * nsg + 16) * sizeof(uint32_t)))) return rc;
+    sgs.seg_bytes = sp.seg_bytes; sgs.max_segs = sp.max_segs;
+    sgs.segs = (ZkSeg *)c.seg_tab.p; sgs.nsegs = (uint32_t *)c.seg_cnt.p; sgs.segn = sgs.nsegs + count;
+    sgs.holes = (ZkHole *)c.seg_holes.p; sgs.tilecnt = (uint32_t *)c.seg_tiles.p;
+    return 0;
+}
+// checksums WHILE the executor writes (zk_k_xxh64_follow, zk_decode.hip): the executor publishes a progress word per frame, the
+// checksum waves run on the context's second queue beside it, the ordinary pass behind the executor takes what they left
+int zk_dec_follow_prepare(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, uint32_t count, uint64_t **prog)
+{
+    int rc;
+    if ((rc = zk_devbuf_reserve(e, c.prog, (size_t)count * sizeof(uint64_t)))) return rc;
+    if ((rc = zk_dec_ctx_aux(e, c))) return rc;
+    *prog = (uint64_t *)c.prog.p;
+    ZK_HIP(hipMemsetAsync(*prog, 0, (size_t)count * sizeof(uint64_t), st));
+    return 0;
+}
+int zk_dec_fork(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st)
+{
+    ZK_HIP(hipEventRecord(c.ev_fork, st));
+    ZK_HIP(hipStreamWaitEvent(c.aux, c.ev_fork, 0));
+    return 0;
+}
+int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, const ZkSegScratch *sgs, const ZkKernelChoice &kc,
+                          bool dense, uint64_t *prog, const uint32_t *rep_init)
+{
+    const uint8_t *comp = (const uint8_t *)a.d_comp, *lit = (const uint8_t *)c.lit.p;
+    uint8_t *dst = (uint8_t *)a.d_dst;
+    const uint64_t *d_off = (const uint64_t *)a.d_d_off;
+    const ZkBlock *blocks = (const ZkBlock *)c.blocks.p;
+    const ZkFrameBase *bases = (const ZkFrameBase *)c.bases.p;
+    const ZkSeqP *seqs = (const ZkSeqP *)c.seqs.p;
+    ZkFrameInfo *infos = (ZkFrameInfo *)c.infos.p;
+    const uint64_t *x_off = a.out_off ? a.out_off : d_off;   // packed indexed output: out_off (count + 1 prefix sums) doubles as the d_off of the checksum kernels
+    const uint32_t x_first = a.out_off ? 0 : a.first;
+    if (sgs) { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec_seg(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, *sgs, kc, dense, prog); }
+    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, (const uint8_t *)a.d_prefix, a.d_prefix ? a.prefix_len : 0, kc, dense, prog, rep_init); }
+    if (a.mark_exec) ZK_HIP(hipEventRecord(c.ev_exec, st));
+    if (prog) {
+        // enqueued BEHIND the executor's launch: were the two queues ever served one after the other, the checksum waves would find
+        // finished frames, not wait (ZK_FOLLOW_PATIENCE) for an executor that cannot start
+        zk_launch_xxh64_follow(c.aux, dst, x_off, x_first, a.count, infos, prog);
+        ZK_HIP(hipEventRecord(c.ev_join, c.aux));
+        ZK_HIP(hipStreamWaitEvent(st, c.ev_join, 0));
+        zk_launch_xxh64(st, dst, x_off, x_first, a.count, infos, nullptr, e->choice, prog);
+    } else if (a.verify) { zk_kernel_timer t(e, ZK_K_XXH64, st); zk_launch_xxh64(st, dst, x_off, x_first, a.count, infos, nullptr, e->choice); }
+    return 0;
+}
+
+// Enqueue the whole decode on the context's queues.  Blocks the host once, for the block / sequence / literal totals
+// that size the scratch (72 bytes, after the two cheapest kernels); returns with the rest still running.
+int zk_decode_enqueue(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a_in)
 {
     // the engine's dictionary: its content is the prefix of every frame, its repeat offsets their first history, its tables the
     // ones in force at their first block (ZSTD_DCtx_loadDictionary)
@@ -275,121 +322,68 @@ int zk_decode_enqueue(zk_engine *e, zk_dec_ctx &c, const zk_dec_args &a_in)
     if (with_dict && e->dict.content_len) { a.d_prefix = e->dict.d_content; a.prefix_len = e->dict.content_len; }
     // history positions are 32-bit words biased by 2^30 (zk_device.h): a frame plus its prefix must fit below that
     if (a.d_prefix && a.prefix_len > ZK_MAX_PREFIX) return -(int)ZK_E_WINDOW_TOO_LARGE;
-    hipStream_t st = c.st;
-    const uint8_t *comp = (const uint8_t *)a.d_comp;
-    const uint64_t *c_off = (const uint64_t *)a.d_c_off, *d_off = (const uint64_t *)a.d_d_off;
-    const uint32_t first = a.first, count = a.count;
+    const uint32_t count = a.count;
     int rc;
-    if ((rc = zk_devbuf_reserve(e, c.infos, (size_t)count * sizeof(ZkFrameInfo)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.bases, (size_t)count * sizeof(ZkFrameBase)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.words, 16 * sizeof(uint64_t)))) return rc;
-    ZkFrameInfo *infos = (ZkFrameInfo *)c.infos.p;
-    ZkFrameBase *bases = (ZkFrameBase *)c.bases.p;
-    uint64_t *words = (uint64_t *)c.words.p;          // [0..2] totals, [3] first error
-
+    if ((rc = zk_dec_frame_tables(e, c, count))) return rc;
+    uint64_t *words = (uint64_t *)c.words.p;
     zk_profile_begin(e);
-    { zk_kernel_timer t(e, ZK_K_WALK_COUNT, st); zk_launch_walk(st, comp, a.comp_size, c_off, d_off, first, count, a.ids, a.out_off, a.dst_cap, nullptr, nullptr, infos, zk_dict_walk_args(e, with_dict, 0, false)); }
-    { zk_kernel_timer t(e, ZK_K_SCAN, st); zk_launch_scan(st, infos, count, bases, words, d_off, first, a.out_off); }
-    ZK_HIP(hipMemcpyAsync(c.h_words, words, 9 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    const uint64_t nblocks = c.h_words[0], nseq = c.h_words[1], nlit = c.h_words[2];
-    const bool verify = a.verify && c.h_words[8] != 0;    // (a batch without a Content_Checksum: zeekstd's library default, encode.rs:163-167 -- no checksum kernel is launched)
-    const uint32_t n_own = (uint32_t)c.h_words[4];        // blocks that need per-block sequence tables
+    if ((rc = zk_dec_count_pass(e, c, st, a, with_dict, ZK_SCAN_WORDS))) return rc;
+    const uint64_t nblocks = c.h_words[ZK_SCAN_BLOCKS], nseq = c.h_words[ZK_SCAN_SEQS], nlit = c.h_words[ZK_SCAN_LITS], out_bytes = c.h_words[ZK_SCAN_OUT_BYTES];
+    const uint32_t n_own = (uint32_t)c.h_words[ZK_SCAN_OWN_TABLES];
+    a.verify = a.verify && c.h_words[ZK_SCAN_CHECKSUMMED] != 0;    // (a batch without a Content_Checksum: zeekstd's library default, encode.rs:163-167 -- no checksum kernel is launched)
     // the pass behind the shared-table kernels has to run whenever a dictionary lends tables (zk_launch_fse_rest)
     const bool rest_always = with_dict && e->dict.tables;
-    const bool dense = nseq * 10 > c.h_words[5];          // fewer than 10 output bytes per sequence (zk_launch_exec)
-    const uint64_t out_bytes = c.h_words[5], max_frame = c.h_words[7];
-    if (nblocks > 0xFFFFFFF0ull) return -(int)ZK_E_GENERIC;
-    if ((rc = zk_devbuf_reserve(e, c.blocks, (size_t)(nblocks + 1) * sizeof(ZkBlock)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.seqs, (size_t)(nseq + 1) * sizeof(ZkSeqP)))) return rc;
+    const bool dense = nseq * 10 > out_bytes;                // fewer than 10 output bytes per sequence (zk_launch_exec)
+    ZkDecShape shape = zk_dec_shape(e, count, out_bytes, c.h_words[ZK_SCAN_MAX_FRAME], nblocks, a.d_prefix != nullptr, a.alone);
+    if ((rc = zk_dec_block_scratch(e, c, nblocks, nseq))) return rc;
     if ((rc = zk_devbuf_reserve(e, c.lit, (size_t)nlit + 64))) return rc;
     ZkBlock *blocks = (ZkBlock *)c.blocks.p;
     ZkSeqP *seqs = (ZkSeqP *)c.seqs.p;
     uint8_t *lit = (uint8_t *)c.lit.p;
-
+    const uint8_t *comp = (const uint8_t *)a.d_comp;
     c.h_words[3] = ~0ull;
     ZK_HIP(hipMemcpyAsync(words + 3, c.h_words + 3, sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    // checksums WHILE the executor writes (zk_k_xxh64_follow, zk_decode.hip): the executor publishes a progress word per frame, the
-    // checksum waves run on the context's second queue beside it, the ordinary pass behind the executor takes what they left
-    // (not in the host pipeline's chunks: they overlap whole chunks on one queue per context, PCIe bounds them, and the extra queues
+    // the checksums beside the executor (zk_dec_follow_prepare)?  (not in the host pipeline's chunks: they overlap whole chunks on one queue per context, PCIe bounds them, and the extra queues
     //  cost the copy queues 1-2 %: 46.4 -> 45.3 GiB/s end to end)
-    const bool follow = verify && !a.single_queue && zk_follow_wanted(e, count, c.h_words[5], a.alone);      // (in segments: behind the fill pass's progress words)
+    const bool follow = shape.follow = a.verify && !a.single_queue && zk_follow_wanted(shape);      // (in segments: behind the fill pass's progress words)
     // The executor in segments (several workgroups per frame; zk_device.h): where a frame is long and the frames alone do not fill the device.
+    const ZkSegPlan sp = zk_seg_plan_dev(shape);
     ZkSegScratch sgs{};
-    const bool seg = zk_seg_wanted(e, a, count, out_bytes, max_frame, nblocks, follow);
-    if (seg) {
-        zk_engine::DecCtx &x = e->dctx[c.slot];
-        sgs.seg_bytes = e->choice.seg_kib ? (uint32_t)e->choice.seg_kib << 10 : ZK_SEG_BYTES;
-        sgs.max_segs = 2u * (uint32_t)((max_frame + sgs.seg_bytes - 1) / sgs.seg_bytes) + 1u;
-        const uint64_t nsg = (uint64_t)count * sgs.max_segs;
-        if ((rc = zk_devbuf_reserve(e, x.seg_tab, (size_t)nsg * sizeof(ZkSeg)))) return rc;
-        if ((rc = zk_devbuf_reserve(e, x.seg_cnt, (size_t)(nsg + count) * sizeof(uint32_t)))) return rc;
-        if ((rc = zk_devbuf_reserve(e, x.seg_holes, (size_t)((out_bytes >> 2) + 16 * nsg + 16) * sizeof(ZkHole)))) return rc;
-        if ((rc = zk_devbuf_reserve(e, x.seg_tiles, (size_t)((out_bytes >> 10) + 2 * nblocks + 8 * nsg + 16) * sizeof(uint32_t)))) return rc;
-        sgs.segs = (ZkSeg *)x.seg_tab.p; sgs.nsegs = (uint32_t *)x.seg_cnt.p; sgs.segn = sgs.nsegs + count;
-        sgs.holes = (ZkHole *)x.seg_holes.p; sgs.tilecnt = (uint32_t *)x.seg_tiles.p;
-    }
+    if (sp.on && (rc = zk_dec_seg_scratch(e, c, count, sp, out_bytes, nblocks, sgs))) return rc;
     ZkKernelChoice kc = e->choice;
     if (follow && !kc.exec_resident) kc.exec_resident = 4;
     uint64_t *prog = nullptr;
-    if (follow) {
-        zk_engine::DecCtx &x = e->dctx[c.slot];
-        if ((rc = zk_devbuf_reserve(e, x.prog, (size_t)count * sizeof(uint64_t)))) return rc;
-        if ((rc = zk_dec_ctx_aux(e, c.slot))) return rc;
-        prog = (uint64_t *)x.prog.p;
-        ZK_HIP(hipMemsetAsync(prog, 0, (size_t)count * sizeof(uint64_t), st));
-    }
+    if (follow && (rc = zk_dec_follow_prepare(e, c, st, count, &prog))) return rc;
     ZK_HIP(hipMemsetAsync(words + 6, 0, sizeof(uint64_t), st));
-    { zk_kernel_timer t(e, ZK_K_WALK_FILL, st); zk_launch_walk(st, comp, a.comp_size, c_off, d_off, first, count, a.ids, a.out_off, a.dst_cap, bases, blocks, infos, zk_dict_walk_args(e, with_dict, nblocks, true)); }
+    zk_dec_walk(e, c, st, a, with_dict, nblocks, true);
     // literals (huf) and sequences (fse) of a block are independent: the two kernels run side by side on two queues;
     // with per-kernel timing on they are serialised instead
     // ... or, where the sequences would get zk_k_fse_predef_fed, both in one kernel whose workgroups each bring a Huffman half and a
     // sequence half (zk_k_entropy_frame: no second queue, no events)
-    const bool fused = !e->profiling && !a.single_queue && zk_entropy_fused_wanted((uint32_t)nblocks, n_own, e->choice, count);
-    e->dctx[c.slot].fused = fused;
-    if (fused) zk_launch_entropy(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, lit, e->choice, rest_always);
+    c.fused = !e->profiling && !a.single_queue && zk_entropy_fused_wanted((uint32_t)nblocks, n_own, e->choice, count);
+    if (c.fused) zk_launch_entropy(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, lit, e->choice, rest_always);
     else if (e->profiling || a.single_queue) {
         { zk_kernel_timer t(e, ZK_K_HUF, st); zk_launch_huf(st, comp, blocks, (uint32_t)nblocks, lit); }
         { zk_kernel_timer t(e, ZK_K_FSE, st); zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count, rest_always); }
     } else {
-        if ((rc = zk_dec_ctx_aux(e, c.slot))) return rc;
-        zk_engine::DecCtx &x = e->dctx[c.slot];
-        ZK_HIP(hipEventRecord(x.ev_fork, st));
-        ZK_HIP(hipStreamWaitEvent(x.aux, x.ev_fork, 0));
-        zk_launch_huf(x.aux, comp, blocks, (uint32_t)nblocks, lit);
-        ZK_HIP(hipEventRecord(x.ev_join, x.aux));
+        if ((rc = zk_dec_ctx_aux(e, c)) || (rc = zk_dec_fork(e, c, st))) return rc;
+        zk_launch_huf(c.aux, comp, blocks, (uint32_t)nblocks, lit);
+        ZK_HIP(hipEventRecord(c.ev_join, c.aux));
         zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count, rest_always);
-        ZK_HIP(hipStreamWaitEvent(st, x.ev_join, 0));
+        ZK_HIP(hipStreamWaitEvent(st, c.ev_join, 0));
     }
-    const uint64_t *x_off = a.out_off ? a.out_off : d_off;   // packed indexed output: out_off (count + 1 prefix sums) doubles as the d_off of the checksum kernels
-    const uint32_t x_first = a.out_off ? 0 : first;
-    if (follow) {
-        zk_engine::DecCtx &x = e->dctx[c.slot];
-        ZK_HIP(hipEventRecord(x.ev_fork, st));               // (in front of the executor: the checksum waves start with it)
-        ZK_HIP(hipStreamWaitEvent(x.aux, x.ev_fork, 0));
-    }
-    if (seg) { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec_seg(st, comp, d_off, first, count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, (uint8_t *)a.d_dst, sgs, kc, dense, prog); }
-    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, first, count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, (uint8_t *)a.d_dst, (const uint8_t *)a.d_prefix, a.d_prefix ? a.prefix_len : 0, kc, dense, prog, with_dict ? e->dict.rep : nullptr); }
-    if (a.mark_exec) ZK_HIP(hipEventRecord(c.ev_exec, st));
-    if (follow) {
-        // enqueued BEHIND the executor's launch: were the two queues ever served one after the other, the checksum waves would find
-        // finished frames, not wait (ZK_FOLLOW_PATIENCE) for an executor that cannot start
-        zk_engine::DecCtx &x = e->dctx[c.slot];
-        zk_launch_xxh64_follow(x.aux, (const uint8_t *)a.d_dst, x_off, x_first, count, infos, prog);
-        ZK_HIP(hipEventRecord(x.ev_join, x.aux));
-        ZK_HIP(hipStreamWaitEvent(st, x.ev_join, 0));
-        zk_launch_xxh64(st, (const uint8_t *)a.d_dst, x_off, x_first, count, infos, nullptr, e->choice, prog);
-    } else if (verify) { zk_kernel_timer t(e, ZK_K_XXH64, st); zk_launch_xxh64(st, (const uint8_t *)a.d_dst, x_off, x_first, count, infos, nullptr, e->choice); }
-    { zk_kernel_timer t(e, ZK_K_STATUS, st); zk_launch_status(st, infos, count, (int32_t *)a.d_frame_status, words + 3, prog, words + 6); }
+    if (follow && (rc = zk_dec_fork(e, c, st))) return rc;  // (in front of the executor: the checksum waves start with it)
+    if ((rc = zk_dec_exec_checksums(e, c, st, a, sp.on ? &sgs : nullptr, kc, dense, prog, with_dict ? e->dict.rep : nullptr))) return rc;
+    { zk_kernel_timer t(e, ZK_K_STATUS, st); zk_launch_status(st, (const ZkFrameInfo *)c.infos.p, count, (int32_t *)a.d_frame_status, words + 3, prog, words + 6); }
     ZK_HIP(hipMemcpyAsync(c.h_words + 3, words + 3, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     return 0;
 }
-int zk_decode_finish(zk_engine *e, zk_dec_ctx &c)
+int zk_decode_finish(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st)
 {
-    ZK_HIP(hipStreamSynchronize(c.st));
+    ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
     zk_profile_collect(e);
-    e->entropy_fused = e->dctx[c.slot].fused;
+    e->entropy_fused = c.fused;
     e->followed = c.h_words[6] & 0xFFFFFFFFull;          // (the high half counts frames the checksum waves hashed and found different)
     if (c.h_words[3] != ~0ull) return -(int)(uint32_t)(c.h_words[3] & 0xFFFFFFFFu);
     return 0;
@@ -401,12 +395,13 @@ static int zk_decode_impl(zk_engine *e, const zk_dec_args &a, void *stream)
     if (a.count == 0) return 0;
     if (e->slot_busy[0]) return ZK_ERR_ARGUMENT;            // a submitted batch still owns context 0: zk_decode_wait first
     ZK_HIP(hipSetDevice(e->device));
-    zk_dec_ctx c = zk_dec_context(e, 0, stream);
+    zk_engine::DecCtx &c = e->dctx[0];
+    hipStream_t st = zk_dec_stream(e, c, stream);
     zk_dec_args b = a;
     b.alone = !e->slot_busy[1];                             // (a batch submitted on the other context would be its neighbour)
-    int rc = zk_decode_enqueue(e, c, b);
+    int rc = zk_decode_enqueue(e, c, st, b);
     if (rc) return rc;
-    return zk_decode_finish(e, c);
+    return zk_decode_finish(e, c, st);
 }
 
 extern "C" int zk_decode_submit_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off,
@@ -417,12 +412,10 @@ extern "C" int zk_decode_submit_dev(zk_engine *e, const void *d_comp, uint64_t c
     const int slot = e->next_slot;
     if (e->slot_busy[slot]) return ZK_ERR_ARGUMENT;         // both contexts in flight: zk_decode_wait the older one first
     ZK_HIP(hipSetDevice(e->device));
-    zk_dec_ctx c = zk_dec_context(e, slot, nullptr);
-    const bool prof = e->profiling;
-    e->profiling = false;                                   // per-kernel events belong to the synchronous path
+    zk_engine::DecCtx &c = e->dctx[slot];
+    zk_profiling_off quiet(e);                              // per-kernel events belong to the synchronous path
     zk_dec_args a{d_comp, comp_size, d_c_off, d_d_off, first, count, nullptr, nullptr, d_dst, dst_cap, verify, d_frame_status, nullptr, 0};
-    int rc = zk_decode_enqueue(e, c, a);
-    e->profiling = prof;
+    int rc = zk_decode_enqueue(e, c, c.st, a);
     if (rc) { (void)hipStreamSynchronize(c.st); return rc; }
     e->slot_busy[slot] = true;
     e->next_slot = slot ^ 1;
@@ -434,11 +427,8 @@ extern "C" int zk_decode_wait(zk_engine *e, int slot)
 {
     if (!e || slot < 0 || slot > 1 || !e->slot_busy[slot]) return ZK_ERR_ARGUMENT;
     ZK_HIP(hipSetDevice(e->device));
-    zk_dec_ctx c = zk_dec_context(e, slot, nullptr);
-    const bool prof = e->profiling;
-    e->profiling = false;
-    const int rc = zk_decode_finish(e, c);
-    e->profiling = prof;
+    zk_profiling_off quiet(e);
+    const int rc = zk_decode_finish(e, e->dctx[slot], e->dctx[slot].st);
     e->slot_busy[slot] = false;
     return rc;
 }
@@ -537,30 +527,20 @@ extern "C" int zk_frame_content_sizes_dev(zk_engine *e, const void *d_comp, uint
     if (count == 0) return 0;
     if (e->slot_busy[0]) return ZK_ERR_ARGUMENT;
     ZK_HIP(hipSetDevice(e->device));
-    zk_dec_ctx c = zk_dec_context(e, 0, stream);
-    hipStream_t st = c.st;
-    const uint8_t *comp = (const uint8_t *)d_comp;
-    const uint64_t *c_off = (const uint64_t *)d_c_off;
-    int rc;
-    if ((rc = zk_devbuf_reserve(e, c.infos, (size_t)count * sizeof(ZkFrameInfo)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.bases, (size_t)count * sizeof(ZkFrameBase)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.words, 16 * sizeof(uint64_t)))) return rc;
-    ZkFrameInfo *infos = (ZkFrameInfo *)c.infos.p;
-    ZkFrameBase *bases = (ZkFrameBase *)c.bases.p;
-    uint64_t *words = (uint64_t *)c.words.p;
+    zk_engine::DecCtx &c = e->dctx[0];
+    hipStream_t st = zk_dec_stream(e, c, stream);
+    zk_profiling_off quiet(e);                              // (no per-kernel events here)
+    const zk_dec_args a{d_comp, comp_size, d_c_off, nullptr, first, count, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0};
     const bool with_dict = zk_dict_applies(e, nullptr);
-    zk_launch_walk(st, comp, comp_size, c_off, nullptr, first, count, nullptr, nullptr, 0, nullptr, nullptr, infos, zk_dict_walk_args(e, with_dict, 0, false));
-    zk_launch_scan(st, infos, count, bases, words, nullptr, first, nullptr);
-    ZK_HIP(hipMemcpyAsync(c.h_words, words, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    const uint64_t nblocks = c.h_words[0], nseq = c.h_words[1];
-    if (nblocks > 0xFFFFFFF0ull) return -(int)ZK_E_GENERIC;
-    if ((rc = zk_devbuf_reserve(e, c.blocks, (size_t)(nblocks + 1) * sizeof(ZkBlock)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.seqs, (size_t)(nseq + 1) * sizeof(ZkSeqP)))) return rc;
+    int rc;
+    if ((rc = zk_dec_frame_tables(e, c, count))) return rc;
+    if ((rc = zk_dec_count_pass(e, c, st, a, with_dict, 6))) return rc;
+    const uint64_t nblocks = c.h_words[ZK_SCAN_BLOCKS];
+    if ((rc = zk_dec_block_scratch(e, c, nblocks, c.h_words[ZK_SCAN_SEQS]))) return rc;
+    zk_dec_walk(e, c, st, a, with_dict, nblocks, true);
     ZkBlock *blocks = (ZkBlock *)c.blocks.p;
-    zk_launch_walk(st, comp, comp_size, c_off, nullptr, first, count, nullptr, nullptr, 0, bases, blocks, infos, zk_dict_walk_args(e, with_dict, nblocks, true));
-    zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, (uint32_t)c.h_words[4], (ZkSeqP *)c.seqs.p, e->choice, count, with_dict && e->dict.tables);
-    zk_launch_frame_sizes(st, infos, bases, blocks, count, (uint64_t *)d_sizes, (int32_t *)d_frame_status);
+    zk_launch_fse(st, (const uint8_t *)d_comp, blocks, (uint32_t)nblocks, (uint32_t)c.h_words[ZK_SCAN_OWN_TABLES], (ZkSeqP *)c.seqs.p, e->choice, count, with_dict && e->dict.tables);
+    zk_launch_frame_sizes(st, (const ZkFrameInfo *)c.infos.p, (const ZkFrameBase *)c.bases.p, blocks, count, (uint64_t *)d_sizes, (int32_t *)d_frame_status);
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
     return 0;

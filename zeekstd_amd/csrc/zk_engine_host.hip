@@ -421,12 +421,10 @@ static int zk_decode_small(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src
     for (uint32_t k = 0; k < count; k++) h_status[k] = -1;
 
     // scratch from bounds the host knows: every sequence regenerates >= 3 bytes, literals never exceed the output
-    zk_dec_ctx c = zk_dec_context(e, 0, nullptr);
+    zk_engine::DecCtx &c = e->dctx[0];
     zk_hostpipe::Slot &s = hp->slot[0];
     const uint32_t block_cap = (uint32_t)(1024 + dsz / 1024 + 8ull * count);
-    if ((rc = zk_devbuf_reserve(e, c.infos, (size_t)count * sizeof(ZkFrameInfo)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.bases, (size_t)count * sizeof(ZkFrameBase)))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.words, 16 * sizeof(uint64_t)))) return rc;
+    if ((rc = zk_dec_frame_tables(e, c, count))) return rc;
     if ((rc = zk_devbuf_reserve(e, c.blocks, (size_t)(block_cap + 1) * sizeof(ZkBlock)))) return rc;
     const uint64_t seq_cap = dsz / 3 + count + 1 + 8ull * (block_cap + 1);        // record slots: what the walk may hand out (it checks)
     if ((rc = zk_devbuf_reserve(e, c.seqs, (size_t)seq_cap * sizeof(ZkSeqP)))) return rc;     // (+ 7 per block: a block's records start on a 64-byte line)
@@ -445,66 +443,31 @@ static int zk_decode_small(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src
     uint32_t groups = (block_cap + 15) / 16;
     if (groups > 32) groups = 32;
     zk_launch_small_entropy(st, comp, blocks, words, (uint8_t *)c.lit.p, (ZkSeqP *)c.seqs.p, groups, e->choice.small_path == 2);
+    uint64_t max_frame = 0;
+    for (uint32_t k = 0; k < count; k++) { const uint64_t d = d_off[first + k + 1] - d_off[first + k]; max_frame = d > max_frame ? d : max_frame; }
+    ZkDecShape shape = zk_dec_shape(e, count, dsz, max_frame, 0, d_prefix != nullptr, true);
     // long frames (a handful of 2 MiB ones: configs[0]): their checksum chains -- 2.9 ms per 2 MiB, twice what the executor takes --
     // start with the executor, on the context's second queue (zk_k_xxh64_follow; zk_follow_wanted)
     uint64_t *prog = nullptr;
-    if (verify && zk_follow_wanted(e, count, dsz, true)) {
-        zk_engine::DecCtx &x = e->dctx[0];
-        if ((rc = zk_devbuf_reserve(e, x.prog, (size_t)count * sizeof(uint64_t)))) return rc;
-        if ((rc = zk_dec_ctx_aux(e, 0))) return rc;
-        prog = (uint64_t *)x.prog.p;
-        ZK_HIP(hipMemsetAsync(prog, 0, (size_t)count * sizeof(uint64_t), st));
-        ZK_HIP(hipEventRecord(x.ev_fork, st));
-        ZK_HIP(hipStreamWaitEvent(x.aux, x.ev_fork, 0));
-    }
-    // long frames (a read of one or two 2 MiB frames -- zeekstd's default frame size): the executor in segments, several workgroups per
-    // frame (zk_k_seg_prep / zk_k_exec_seg / zk_k_exec_fill_lds: 1.37 -> 0.6 ms for a 2 MiB frame); the host knows the frames' sizes here
-    // ... and SHORT frames in a handful (a seek into 64 KiB frames: sixteen blocks of 4 KiB as this encoder writes them, executed one
-    // after the other at ~7 us each by a frame's workgroup): a segment per block, all at once, and one turn of the fill pass for the frame
-    uint64_t max_frame = 0;
-    for (uint32_t k = 0; k < count; k++) { const uint64_t d = d_off[first + k + 1] - d_off[first + k]; max_frame = d > max_frame ? d : max_frame; }
-    const bool long_frames = dsz >= (uint64_t)count * (4u * ZK_SEG_BYTES);
-    const uint32_t seg_bytes = e->choice.seg_kib ? (uint32_t)e->choice.seg_kib << 10 : long_frames ? ZK_SEG_BYTES : 4096u;
-    const uint64_t max_segs64 = 2 * ((max_frame + seg_bytes - 1) / seg_bytes) + 1;
-    bool short_frames = !long_frames && max_frame >= 32768 && max_frame <= ZK_SEG_BYTES && (uint64_t)count * max_segs64 <= 256;
-    if (short_frames && e->choice.exec_seg != 2) {
-        // ... if they HAVE blocks to deal out: the reference's own 64 KiB frames are one block (+ an empty last one), executed by one
-        // workgroup either way -- the extra launches would only cost them ~25 us.  The host holds the frames' bytes (pinned, just
-        // filled): the walk over a handful of block headers is the device's lane code, run here (zk_walk_frame is host + device)
-        uint32_t nb = 0;
-        for (uint32_t k = 0; k < count && short_frames; k++) {
+    if (verify && zk_follow_wanted(shape) && ((rc = zk_dec_follow_prepare(e, c, st, count, &prog)) || (rc = zk_dec_fork(e, c, st)))) return rc;
+    // the executor in segments for long frames, and for short ones that have blocks to deal out (zk_seg_plan_small).  The host holds the
+    // frames' bytes (pinned, just filled): the walk over a handful of block headers is the device's lane code, run here (zk_walk_frame
+    // is host + device)
+    if (zk_small_wants_blocks(shape)) {
+        uint64_t nb = 0;
+        for (uint32_t k = 0; k < count; k++) {
             ZkFrameInfo fi;
             zk_walk_frame(h_comp, h_offs[k], h_offs[k + 1], h_offs[count + 1 + k + 1] - h_offs[count + 1 + k], k, nullptr, nullptr, fi);
-            if (fi.status != ZK_OK) short_frames = false;          // (the device gives the verdict)
+            if (fi.status != ZK_OK) { nb = 0; break; }             // (the device gives the verdict)
             nb += fi.n_blocks;
         }
-        short_frames = short_frames && nb >= 6u * count;
+        shape.nblocks = nb;
     }
-    const bool seg = !d_prefix && e->choice.exec_seg != 1 && max_segs64 <= 65535 && (e->choice.exec_seg == 2 || long_frames || short_frames);
-    if (seg) {
-        zk_engine::DecCtx &x = e->dctx[0];
-        ZkSegScratch sgs{};
-        sgs.seg_bytes = seg_bytes;
-        sgs.max_segs = (uint32_t)max_segs64;
-        const uint64_t nsg = (uint64_t)count * sgs.max_segs;
-        if ((rc = zk_devbuf_reserve(e, x.seg_tab, (size_t)nsg * sizeof(ZkSeg)))) return rc;
-        if ((rc = zk_devbuf_reserve(e, x.seg_cnt, (size_t)(nsg + count) * sizeof(uint32_t)))) return rc;
-        if ((rc = zk_devbuf_reserve(e, x.seg_holes, (size_t)((dsz >> 2) + 16 * nsg + 16) * sizeof(ZkHole)))) return rc;
-        if ((rc = zk_devbuf_reserve(e, x.seg_tiles, (size_t)((dsz >> 10) + 2 * (uint64_t)block_cap + 8 * nsg + 16) * sizeof(uint32_t)))) return rc;
-        sgs.segs = (ZkSeg *)x.seg_tab.p; sgs.nsegs = (uint32_t *)x.seg_cnt.p; sgs.segn = sgs.nsegs + count;
-        sgs.holes = (ZkHole *)x.seg_holes.p; sgs.tilecnt = (uint32_t *)x.seg_tiles.p;
-        zk_launch_exec_seg(st, comp, d_offs + count + 1, 0, count, nullptr, nullptr, blocks, (const ZkFrameBase *)c.bases.p, infos, (const ZkSeqP *)c.seqs.p,
-                           (const uint8_t *)c.lit.p, (uint8_t *)s.d_out.p, sgs, e->choice, false, prog);
-    } else
-    zk_launch_exec(st, comp, d_offs + count + 1, 0, count, nullptr, nullptr, blocks, (const ZkFrameBase *)c.bases.p, infos, (const ZkSeqP *)c.seqs.p,
-                   (const uint8_t *)c.lit.p, (uint8_t *)s.d_out.p, (const uint8_t *)d_prefix, d_prefix ? prefix_len : 0, e->choice, false, prog);
-    if (prog) {
-        zk_engine::DecCtx &x = e->dctx[0];
-        zk_launch_xxh64_follow(x.aux, (const uint8_t *)s.d_out.p, d_offs + count + 1, 0, count, infos, prog);
-        ZK_HIP(hipEventRecord(x.ev_join, x.aux));
-        ZK_HIP(hipStreamWaitEvent(st, x.ev_join, 0));
-        zk_launch_xxh64(st, (const uint8_t *)s.d_out.p, d_offs + count + 1, 0, count, infos, nullptr, e->choice, prog);
-    } else if (verify) zk_launch_xxh64(st, (const uint8_t *)s.d_out.p, d_offs + count + 1, 0, count, infos, nullptr, e->choice);
+    const ZkSegPlan sp = zk_seg_plan_small(shape);
+    ZkSegScratch sgs{};
+    if (sp.on && (rc = zk_dec_seg_scratch(e, c, count, sp, dsz, block_cap, sgs))) return rc;
+    const zk_dec_args a{comp, csz, d_offs, d_offs + count + 1, 0, count, nullptr, nullptr, s.d_out.p, dsz, verify, s.d_st.p, d_prefix, d_prefix ? prefix_len : 0};
+    if ((rc = zk_dec_exec_checksums(e, c, st, a, sp.on ? &sgs : nullptr, e->choice, false, prog, nullptr))) return rc;
     zk_launch_small_publish(st, infos, d_offs, count, (const uint8_t *)s.d_out.p, dsz ? h_out : nullptr, (int32_t *)s.d_st.p, h_status, words, hp->pin_flag, gen);
     // completion: the last workgroup of the publish kernel writes the generation into pinned memory
     volatile uint32_t *flag = hp->pin_flag;
@@ -644,17 +607,15 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
         zk_hostpipe::Slot &s = hp->slot[i % nslots];
         const uint32_t nf = ck.f1 - ck.f0;
         const uint64_t dsz = ck.d1 - ck.d0;
-        zk_dec_ctx c = zk_dec_context(e, (int)(i % nctx), nullptr);
+        zk_engine::DecCtx &c = e->dctx[i % nctx];
         ZK_HIP(hipStreamWaitEvent(c.st, s.ev_in, 0));
         if (s.out_pending) ZK_HIP(hipStreamWaitEvent(c.st, s.ev_out, 0));
         const uint64_t *dc = (const uint64_t *)s.d_off.p, *dd = dc + nf + 1;
         zk_dec_args a{s.d_in.p, ck.c1 - ck.c0, dc, dd, 0, nf, nullptr, nullptr, s.d_out.p, dsz, verify, s.d_st.p, d_prefix, d_prefix ? prefix_len : 0};
         a.single_queue = nchunks > 1;                       // whole chunks overlap instead of huf || fse
         a.mark_exec = true;                                 // the bytes travel back while the checksum chains still run; the status words follow them
-        const bool prof = e->profiling;
-        if (nchunks > 1) e->profiling = false;              // per-kernel events describe one synchronous batch
-        int r = zk_decode_enqueue(e, c, a);
-        e->profiling = prof;
+        zk_profiling_off quiet(e, nchunks > 1);             // per-kernel events describe one synchronous batch
+        int r = zk_decode_enqueue(e, c, c.st, a);
         if (r) return r;
         ZK_HIP(hipEventRecord(s.ev_dec, c.st));
         ZK_HIP(hipStreamWaitEvent(hp->s_d2h, c.ev_exec, 0));
@@ -833,10 +794,8 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
         zk_enc_args a{s.d_src.p, bn, frame_size, level, checksum, d_prefix, d_prefix ? prefix_len : 0, s.d_dst.p,
                       zk_compress_bound(bn, frame_size), dc, dd};
         uint32_t nfo = 0;
-        const bool prof = e->profiling;
-        if (nchunks > 1) e->profiling = false;
+        zk_profiling_off quiet(e, nchunks > 1);
         int r = zk_encode_enqueue(e, a, st, &nfo);
-        e->profiling = prof;
         if (r) return r;
         ZK_HIP(hipEventRecord(s.ev_enc, st));
         return 0;

@@ -57,12 +57,11 @@ extern "C" int zk_read_ranges_dev(zk_engine *e, const void *d_comp, uint64_t com
     if (count == 0) return 0;
     if (e->slot_busy[0]) return ZK_ERR_ARGUMENT;            // a submitted batch still owns context 0: zk_decode_wait first
     ZK_HIP(hipSetDevice(e->device));
-    zk_dec_ctx c = zk_dec_context(e, 0, stream);
     zk_engine::DecCtx &x = e->dctx[0];
-    hipStream_t st = c.st;
+    hipStream_t st = zk_dec_stream(e, x, stream);
     int rc;
     if ((rc = zk_devbuf_reserve(e, x.rng_meta, RangeMeta(nullptr, count, n_frames).bytes))) return rc;
-    if ((rc = zk_devbuf_reserve(e, c.words, 16 * sizeof(uint64_t)))) return rc;
+    if ((rc = zk_devbuf_reserve(e, x.words, 16 * sizeof(uint64_t)))) return rc;
     const RangeMeta m(x.rng_meta.p, count, n_frames);
     int32_t *status = d_range_status ? (int32_t *)d_range_status : m.status;
     const ZkRangeArgs r{(const uint64_t *)d_d_off, n_frames, (const uint64_t *)d_offs, (const uint64_t *)d_lens, (const uint64_t *)d_dst_off, count, d_dst, dst_cap};
@@ -106,7 +105,7 @@ extern "C" int zk_read_ranges_dev(zk_engine *e, const void *d_comp, uint64_t com
         if (!rc && a != 0) { zk_launch_range_rebase(st, m.uoff, a, b - a, m.poff); out_off = m.poff; }
         const zk_dec_args da{d_comp, comp_size, d_c_off, d_d_off, 0, b - a, m.ids + a, out_off, x.rng.p, pass_bytes, verify, m.fstat + a, nullptr, 0,
                              /*alone*/ !e->slot_busy[1]};
-        if (!rc) rc = zk_decode_enqueue(e, c, da);
+        if (!rc) rc = zk_decode_enqueue(e, x, st, da);
         if (rc == ZK_ERR_HIP && b - a > 1) {
             (void)hipStreamSynchronize(st);
             (void)hipGetLastError();
@@ -118,11 +117,11 @@ extern "C" int zk_read_ranges_dev(zk_engine *e, const void *d_comp, uint64_t com
         { zk_kernel_timer t(e, ZK_K_RANGE_GATHER, st); zk_launch_range_gather(st, (const uint8_t *)x.rng.p, (uint8_t *)d_dst, m.copies, m.coff, count, pass_bytes); }
         if (b == nt) {      // the last pass: the statuses ride behind it, one synchronisation for both
             zk_kernel_timer t(e, ZK_K_RANGE_STATUS, st);
-            zk_launch_range_status(st, r, m.rfirst, m.rlast, m.slot, m.fstat, any_failed, (const uint64_t *)c.words.p + 3, status, m.words + 2);
+            zk_launch_range_status(st, r, m.rfirst, m.rlast, m.slot, m.fstat, any_failed, (const uint64_t *)x.words.p + 3, status, m.words + 2);
             status_queued = true;
         }
         if (status_queued) ZK_HIP(hipMemcpyAsync(hw + 2, m.words + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        rc = zk_decode_finish(e, c);
+        rc = zk_decode_finish(e, x, st);
         if (rc <= -1000) return rc;
         if (rc) any_failed = true;
         e->ranges_frames += b - a;

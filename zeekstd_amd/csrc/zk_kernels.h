@@ -16,7 +16,7 @@ struct ZkKernelChoice {
     int exec_resident = 0;  // zk_k_exec<256>: workgroups per CU (4 / 5) through LDS the launch asks for and does not use
     int small_path = 0;     // host-pointer decode of <= 64 frames: 1 the general pipeline instead, 2 the small path's entropy roles as two kernels
     int exec_seg = 0;       // the executor in segments (zk_k_seg_prep / zk_k_exec_seg / zk_k_exec_fill): 1 never, 2 always (without a prefix); 0 by batch shape
-    int seg_kib = 0;        // ... output KiB per segment (1..128; 0 = 128)
+    int seg_kib = 0;        // ... output KiB per segment (1..128; 0 = 128, or 4 for short frames on the small path: zk_dec_plan.h)
     int seg_fill = 0;       // ... the fill pass: 1 zk_k_exec_fill<1024> (rounds through memory), 2 zk_k_exec_fill<256>, 3 zk_k_exec_fill_lds (the segment's holes in LDS); 0 by batch size
     int entropy = 0;        // literals and sequences of a batch: 1 zk_k_huf || the sequence kernels on two queues, 2 zk_k_entropy_frame wherever a batch qualifies
                             // (zk_entropy_fused_wanted); 0 by batch shape
