@@ -108,7 +108,10 @@ enum {
     ZK_CHOICE_ENTROPY = 13,       /* literals and sequences of a device-pointer batch: 1 = zk_k_huf beside the sequence kernels on two queues, 2 = one kernel
                                    * (zk_k_entropy_frame) for every batch that qualifies -- no frame with more than one set of own tables -- whatever its
                                    * size; 0 = by batch shape.  zk_engine_entropy_fused says which one ran */
-    ZK_CHOICE_RANGE_PASS_MIB = 14 /* zk_read_ranges*: decoded MiB of scratch per pass (1..2^20; 0 = 1024).  A pass is never less than one frame */
+    ZK_CHOICE_RANGE_PASS_MIB = 14, /* zk_read_ranges*: decoded MiB of scratch per pass (1..2^20; 0 = 1024).  A pass is never less than one frame */
+    ZK_CHOICE_ENC_DENSE_SLICE_KIB = 15 /* encodes with dense far history (level 0 / >= 3, frames beyond the matcher's ring): input KiB whose candidate scratch
+                                        * (8 bytes per input byte) is reserved at a time (1..2^22; 0 = 2^22, 4 GiB).  A longer input is matched slice after
+                                        * slice of whole frames over that scratch, never less than one frame; the bytes produced do not depend on it */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was

@@ -408,3 +408,166 @@ def test_decode_shard_at_the_c_abi(engine, world):
     lo, hi = parallel.shard_range(len(frames), 0, 2)
     with pytest.raises(zk.Error):
         parallel.decode_shard(engine, comp[:int(c_off[hi]) - 1], st, 0, 2)
+
+
+# ---------------------------------------------------------------- the shared transport (zk_pipe_upload, the ring download, the slots)
+@pytest.fixture(scope="module")
+def three_chunks():
+    """529 MiB + 12 345 bytes in 1 MiB frames: three distinct generator blocks, tiled.  530 frames are three encode chunks (256, 256, 18),
+    so the slots are reused (es[i & 1], out_pending), prep(i + 2) runs and both halves of pin_meta carry seek entries.  The expected
+    bytes are the twin's: the three blocks and the ragged tail, four encodes, repeated in frame order."""
+    fs, whole, tail_len = 1 << 20, 529, 12345
+    blocks = [zko.gen_chunks(fs, 410 + k) for k in range(3)]
+    assert len(set(blocks)) == 3
+    data = (b"".join(blocks) * (whole // 3 + 1))[:whole * fs + tail_len]
+    enc = [zko.frame_encode(b, 1, True) for b in blocks] + [zko.frame_encode(data[whole * fs:], 1, True)]
+    want = b"".join([enc[i % 3] for i in range(whole)] + [enc[3]])
+    frames = [(len(enc[i % 3]), fs) for i in range(whole)] + [(len(enc[3]), tail_len)]
+    return data, want, frames
+
+
+@pytest.mark.parametrize("pinned", [False, True], ids=["pageable", "pinned"])
+def test_three_encode_chunks(engine, three_chunks, pinned):
+    """Level 1 with checksums, from pageable memory (registration window, or the ring) and from zk_host_alloc memory (DMA as it is):
+    the whole output and the (c, d) list equal the twin's; the pageable run's output decodes back in 16 MiB chunks."""
+    data, want, want_frames = three_chunks
+    fs, nf = 1 << 20, len(want_frames)
+    if not pinned:
+        comp, frames = engine.encode_frames(np.frombuffer(data, np.uint8), fs, 1, True)
+        assert frames == want_frames
+        assert comp == want
+        c, d = offsets_from_frames(frames)
+        engine.set_kernel_choice(pipe_chunk_mib=16)
+        try:
+            out, st = engine.decode_frames(comp + b"\0" * 8, c, d, verify=True)
+        finally:
+            engine.set_kernel_choice(pipe_chunk_mib=0)
+        assert not st.any() and out == data
+        return
+    lib = zk.lib
+    cap = int(lib.zk_compress_bound(len(data), fs))
+    p_src = lib.zk_host_alloc(len(data))
+    assert p_src
+    try:
+        C.memmove(p_src, data, len(data))
+        out = np.empty(cap, np.uint8)
+        cs = np.zeros(nf, np.uint32); ds = np.zeros(nf, np.uint32)
+        n_out = C.c_uint32(); wr = C.c_uint64()
+        rc = lib.zk_encode_frames(engine._h, p_src, len(data), fs, 1, 1, out.ctypes.data, cap, cs.ctypes.data, ds.ctypes.data, nf, C.byref(n_out), C.byref(wr))
+        assert rc == 0 and n_out.value == nf
+        assert list(zip(cs.tolist(), ds.tolist())) == want_frames
+        assert out[:wr.value].tobytes() == want
+    finally:
+        lib.zk_host_free(p_src)
+
+
+class _ReadOnlyMapping:
+    """`payload` in an anonymous mapping that is read-only by the time anybody else sees its address (.addr)."""
+
+    def __init__(self, payload):
+        import mmap
+        self._libc = C.CDLL(None, use_errno=True)
+        self._libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+        self.size = (len(payload) + mmap.PAGESIZE - 1) // mmap.PAGESIZE * mmap.PAGESIZE
+        self._m = mmap.mmap(-1, self.size)
+        self._m[:len(payload)] = payload
+        self._view = (C.c_char * self.size).from_buffer(self._m)
+        self.addr = C.addressof(self._view)
+        self._prot(mmap.PROT_READ)
+
+    def _prot(self, prot):
+        if self._libc.mprotect(self.addr, self.size, prot) != 0:
+            raise OSError(C.get_errno(), "mprotect")
+
+    def close(self):
+        import mmap
+        self._prot(mmap.PROT_READ | mmap.PROT_WRITE)
+        del self._view
+        self._m.close()
+
+
+def test_source_in_a_read_only_mapping(engine):
+    """A source above 4 MiB (not a small request) in pages that cannot be written: the case ZkRegWindow's comment names as one it cannot
+    register, so every upload is staged through ring_in.  Decode of 6 x 1 MiB frames in 1 MiB chunks (five of them random bytes: the
+    compressed source is above 4 MiB too), and an encode of 6 MiB + 1 against the twin.  Which transport ran cannot be seen from
+    outside and the engine counts nothing for it: where registering such pages succeeds after all, this covers the window's path."""
+    fs = 1 << 20
+    data = zko.gen_random(5 * fs, 77) + zko.gen_chunks(fs + 1, 78)
+    want = b"".join(zko.frame_encode(data[o:o + fs], 1, True) for o in range(0, len(data), fs))
+    lib = zk.lib
+    # decode: the first six frames
+    comp6, frames6 = engine.encode_frames(np.frombuffer(data[:6 * fs], np.uint8), fs, 1, True)
+    assert comp6 == want[:len(comp6)] and len(comp6) > (4 << 20)
+    c, d = offsets_from_frames(frames6)
+    out = np.empty(6 * fs, np.uint8)
+    st = np.zeros(6, np.int32)
+    ro = _ReadOnlyMapping(comp6 + b"\0" * 8)
+    engine.set_kernel_choice(pipe_chunk_mib=1)
+    try:
+        rc = lib.zk_decode_frames(engine._h, ro.addr, len(comp6), c.ctypes.data, d.ctypes.data, 0, 6, out.ctypes.data, out.size, 1, st.ctypes.data)
+    finally:
+        engine.set_kernel_choice(pipe_chunk_mib=0)
+        ro.close()
+    assert rc == 0 and not st.any() and out.tobytes() == data[:6 * fs]
+    # encode: seven frames, the last of one byte
+    cap = int(lib.zk_compress_bound(len(data), fs))
+    dst = np.empty(cap, np.uint8)
+    cs = np.zeros(7, np.uint32); ds = np.zeros(7, np.uint32)
+    n_out = C.c_uint32(); wr = C.c_uint64()
+    ro = _ReadOnlyMapping(data)
+    try:
+        rc = lib.zk_encode_frames(engine._h, ro.addr, len(data), fs, 1, 1, dst.ctypes.data, cap, cs.ctypes.data, ds.ctypes.data, 7, C.byref(n_out), C.byref(wr))
+    finally:
+        ro.close()
+    assert rc == 0 and n_out.value == 7 and ds.tolist() == [fs] * 6 + [1]
+    assert dst[:wr.value].tobytes() == want
+
+
+_ENC_KERNELS = {"zk_k_enc_match", "zk_k_enc_fse_build", "zk_k_enc_xxh64", "zk_k_enc_entropy", "zk_k_enc_compact"}
+
+
+def _timed_level3_encode(engine):
+    """Level-3 device-pointer encode of 4 frames of 300 001 bytes (dense far history) with profiling on -> (bytes, names of the timed kernels)"""
+    import torch
+    fs = 300001
+    data = zko.gen_chunks(4 * fs, 9)
+    dev = torch.device("cuda", 0)
+    d_src = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+    cap = int(zk.lib.zk_compress_bound(len(data), fs))
+    d_dst = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    engine.set_profiling(True)
+    try:
+        nf, written = engine.encode_frames_dev(d_src, len(data), fs, 3, True, d_dst, cap)
+        names = set(engine.kernel_times())
+    finally:
+        engine.set_profiling(False)
+    assert nf == 4
+    return bytes(d_dst[:written].cpu().numpy()), names
+
+
+def test_timed_kernels_of_one_slice_and_of_several(engine):
+    """What an encode times (names, not times): with the dense scratch over the whole input the candidate kernel and the matcher each have
+    their own bracket; cut into slices of one frame (enc_dense_slice_kib=293: 300 032 bytes) the matcher's bracket spans the loop and
+    the candidate kernel has none.  The same bytes either way."""
+    one, names_one = _timed_level3_encode(engine)
+    engine.set_kernel_choice(enc_dense_slice_kib=293)
+    try:
+        sliced, names_sliced = _timed_level3_encode(engine)
+    finally:
+        engine.set_kernel_choice(enc_dense_slice_kib=0)
+    assert names_one == _ENC_KERNELS | {"zk_k_enc_dense_cand"}
+    assert names_sliced == _ENC_KERNELS
+    assert one == sliced
+
+
+def test_dense_slice_choice_key(engine):
+    """ZK_CHOICE_ENC_DENSE_SLICE_KIB takes 0 .. 2^22; ZK_CHOICE_RESET puts the 4 GiB default back (one slice: the candidate kernel is timed again)."""
+    key = engine.CHOICES["enc_dense_slice_kib"]
+    assert key == 15
+    for value in (-1, (1 << 22) + 1):
+        assert zk.lib.zk_engine_set_kernel_choice(engine._h, key, value) == -2003       # ZK_ERR_ARGUMENT
+    engine.set_kernel_choice(enc_dense_slice_kib=1 << 22)
+    engine.set_kernel_choice(enc_dense_slice_kib=293)
+    engine.set_kernel_choice(reset=0)
+    _, names = _timed_level3_encode(engine)
+    assert "zk_k_enc_dense_cand" in names

@@ -67,22 +67,40 @@ struct zk_engine {
     hipEvent_t ev_start[ZK_NKERNELS] = {}, ev_stop[ZK_NKERNELS] = {};
     bool ev_used[ZK_NKERNELS] = {};
     float kernel_ms[ZK_NKERNELS] = {};
-    // encode scratch
-    zk_devbuf enc_a, enc_b, enc_c, enc_d, enc_e, enc_f;
-    void *enc_pin = nullptr; size_t enc_pin_cap = 0;   // pinned host copy of the frame / block lists of the encode in flight
-    zk_devbuf enc_hist;                     // prefix mode: [prefix tail | frame] records for the matcher
-    zk_devbuf enc_seg;                      // frames above ZKE_SEGMENT: the matcher's segment records
-    zk_devbuf enc_dense;                    // dense far history (level 0 / >= 3, frames beyond the ring's reach): a candidate per input byte (ZkEncLdm::dense)
-    zk_devbuf enc_ldm;                      // prefix beyond the matcher's ring: the long-distance table (ZkEncLdm)
-    ZkEncTables enc_tables;
-    bool enc_tables_ready = false;
-    // second queue of the encoder: the checksum kernel (one serial chain per frame) runs beside the matcher (one workgroup
-    // per CU, half of the CU's wave slots free); created on first use
-    hipStream_t enc_aux = nullptr;
-    hipEvent_t enc_ev_fork = nullptr, enc_ev_join = nullptr;
+    // the encoder: one encode in flight (zk_engine_enc.hip).  Device scratch, named as the launchers of zk_kernels.h name what it holds
+    struct Enc {
+        zk_devbuf lists;                    // frames | blocks: the device copy of the pinned lists
+        zk_devbuf seqs;                     // packed sequences, behind them the match positions (mpos)
+        zk_devbuf lits;                     // literals
+        zk_devbuf scratch;                  // per-block output of the entropy stage
+        zk_devbuf words;                    // per frame: c_size64, out_off, hashes, d_off; behind them the predefined tables
+        zk_devbuf ftab;                     // the frames' tables
+        uint8_t *pin = nullptr; size_t pin_cap = 0;   // pinned host copy of the frame / block lists of the encode in flight
+        zk_devbuf hist;                     // prefix mode: [prefix tail | frame] records for the matcher
+        zk_devbuf seg;                      // frames above ZKE_SEGMENT: the matcher's segment records
+        zk_devbuf dense;                    // dense far history (level 0 / >= 3, frames beyond the ring's reach): a candidate per input byte (ZkEncLdm::dense)
+        zk_devbuf ldm;                      // prefix beyond the matcher's ring: the long-distance table (ZkEncLdm)
+        uint64_t dense_slice_bytes = 0;     // input bytes the dense scratch is reserved for (0 = 4 GiB), ZK_CHOICE_ENC_DENSE_SLICE_KIB
+        ZkEncTables tables;
+        bool tables_ready = false;
+        // second queue: the checksum kernel (one serial chain per frame) runs beside the entropy stage; created on first use
+        hipStream_t aux = nullptr;
+        hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    } enc;
 };
 
+// every HIP call of the engine's host code: the error text is kept for zk_engine_last_hip_error
+#define ZK_HIP(call)                                                                                 \
+    do {                                                                                             \
+        hipError_t _e = (call);                                                                      \
+        if (_e != hipSuccess) {                                                                      \
+            e->last_err = std::string(#call) + ": " + hipGetErrorString(_e);                         \
+            return ZK_ERR_HIP;                                                                       \
+        }                                                                                            \
+    } while (0)
+
 int zk_devbuf_reserve(zk_engine *e, zk_devbuf &b, size_t bytes);
+int zk_pin_reserve(zk_engine *e, uint8_t *&p, size_t &cap, size_t bytes);      // the same for a pinned host buffer (contents are not kept)
 
 // ---- decode plumbing shared by zk_engine.hip (device-pointer entry points), zk_engine_host.hip (host pipeline, small path) and
 // zk_engine_ranges.hip.  Every stage takes the context and the queue to run on: zk_dec_stream.
@@ -162,13 +180,13 @@ int zk_engine_stage_prefix(zk_engine *e, const void *owner, const uint8_t *prefi
 // multi-threaded memcpy on the engine's worker threads (large host-side copies of the zeekstd:: classes)
 void zk_host_copy(zk_engine *e, void *dst, const void *src, size_t n);
 
-// RAII-free helper: brackets one launch with events when profiling is on
+// RAII-free helper: brackets one launch with events when profiling is on (and `on`)
 struct zk_kernel_timer {
-    zk_engine *e; int k; hipStream_t st;
-    zk_kernel_timer(zk_engine *e_, int k_, hipStream_t st_) : e(e_), k(k_), st(st_) {
-        if (e->profiling) { (void)hipEventRecord(e->ev_start[k], st); e->ev_used[k] = true; }
+    zk_engine *e; int k; hipStream_t st; bool on;
+    zk_kernel_timer(zk_engine *e_, int k_, hipStream_t st_, bool on_ = true) : e(e_), k(k_), st(st_), on(on_ && e_->profiling) {
+        if (on) { (void)hipEventRecord(e->ev_start[k], st); e->ev_used[k] = true; }
     }
-    ~zk_kernel_timer() { if (e->profiling) (void)hipEventRecord(e->ev_stop[k], st); }
+    ~zk_kernel_timer() { if (on) (void)hipEventRecord(e->ev_stop[k], st); }
 };
 // per-kernel events describe one synchronous batch: everything else runs with profiling off for a scope
 struct zk_profiling_off {

@@ -13,15 +13,6 @@
 #include "zk_kernels.h"
 #include "zk_dict.h"
 
-#define ZK_HIP(call)                                                                                 \
-    do {                                                                                             \
-        hipError_t _e = (call);                                                                      \
-        if (_e != hipSuccess) {                                                                      \
-            e->last_err = std::string(#call) + ": " + hipGetErrorString(_e);                         \
-            return ZK_ERR_HIP;                                                                       \
-        }                                                                                            \
-    } while (0)
-
 int zk_devbuf_reserve(zk_engine *e, zk_devbuf &b, size_t bytes)
 {
     if (bytes <= b.cap) return 0;
@@ -30,6 +21,17 @@ int zk_devbuf_reserve(zk_engine *e, zk_devbuf &b, size_t bytes)
     size_t want = bytes + bytes / 4 + 4096;
     ZK_HIP(hipMalloc(&b.p, want));
     b.cap = want;
+    return 0;
+}
+
+int zk_pin_reserve(zk_engine *e, uint8_t *&p, size_t &cap, size_t bytes)
+{
+    if (bytes <= cap) return 0;
+    if (p) ZK_HIP(hipHostFree(p));
+    p = nullptr; cap = 0;
+    const size_t want = bytes + bytes / 2 + 4096;
+    ZK_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
+    cap = want;
     return 0;
 }
 
@@ -59,7 +61,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     if (!e) return ZK_ERR_ARGUMENT;
     ZkKernelChoice &k = e->choice;
     switch (what) {
-    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; e->range_pass_bytes = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
+    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; e->range_pass_bytes = 0; e->enc.dense_slice_bytes = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
     case ZK_CHOICE_FSE_OWN: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; k.fse_own = value; return 0;
     case ZK_CHOICE_FSE_SHARED: if (value < 0 || value > 3) return ZK_ERR_ARGUMENT; k.fse_shared = value; return 0;
     case ZK_CHOICE_EXEC_LANES: if (value != 0 && value != 128 && value != 256 && value != 512 && value != 1024) return ZK_ERR_ARGUMENT; k.exec_lanes = value; return 0;
@@ -74,6 +76,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     case ZK_CHOICE_PIPE_CONTEXTS: if (value < 0 || value > ZK_MAX_CTX) return ZK_ERR_ARGUMENT; e->pipe_contexts = value; zk_hostpipe_tune(e); return 0;
     case ZK_CHOICE_PIPE_CHUNK_MIB: if (value < 0 || value > 4096) return ZK_ERR_ARGUMENT; e->pipe_chunk_bytes = (uint64_t)value << 20; zk_hostpipe_tune(e); return 0;
     case ZK_CHOICE_RANGE_PASS_MIB: if (value < 0 || value > (1 << 20)) return ZK_ERR_ARGUMENT; e->range_pass_bytes = (uint64_t)value << 20; return 0;
+    case ZK_CHOICE_ENC_DENSE_SLICE_KIB: if (value < 0 || value > (1 << 22)) return ZK_ERR_ARGUMENT; e->enc.dense_slice_bytes = (uint64_t)value << 10; return 0;
     default: return ZK_ERR_ARGUMENT;
     }
 }
@@ -161,10 +164,10 @@ extern "C" void zk_engine_destroy(zk_engine *e)
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
     zk_hostpipe_destroy(e);
-    if (e->enc_pin) (void)hipHostFree(e->enc_pin);
+    if (e->enc.pin) (void)hipHostFree(e->enc.pin);
     for (auto &c : e->dctx) if (c.st) (void)hipStreamSynchronize(c.st);
     zk_devbuf *bufs[] = {&e->dict.buf, &e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc,
-                         &e->enc_a, &e->enc_b, &e->enc_c, &e->enc_d, &e->enc_e, &e->enc_f, &e->enc_hist, &e->enc_seg, &e->enc_ldm, &e->enc_dense};
+                         &e->enc.lists, &e->enc.seqs, &e->enc.lits, &e->enc.scratch, &e->enc.words, &e->enc.ftab, &e->enc.hist, &e->enc.seg, &e->enc.ldm, &e->enc.dense};
     for (zk_devbuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (e->h_words) (void)hipHostFree(e->h_words);
     for (int k = 0; k < ZK_NKERNELS; k++) { if (e->ev_start[k]) (void)hipEventDestroy(e->ev_start[k]); if (e->ev_stop[k]) (void)hipEventDestroy(e->ev_stop[k]); }
@@ -176,8 +179,8 @@ extern "C" void zk_engine_destroy(zk_engine *e)
         if (c.aux) (void)hipStreamDestroy(c.aux);
         if (c.st && i != 0) (void)hipStreamDestroy(c.st);     // context 0 runs on the engine's own stream
     }
-    if (e->enc_aux) { (void)hipStreamSynchronize(e->enc_aux); (void)hipStreamDestroy(e->enc_aux); }
-    for (hipEvent_t ev : {e->enc_ev_fork, e->enc_ev_join}) if (ev) (void)hipEventDestroy(ev);
+    if (e->enc.aux) { (void)hipStreamSynchronize(e->enc.aux); (void)hipStreamDestroy(e->enc.aux); }
+    for (hipEvent_t ev : {e->enc.ev_fork, e->enc.ev_join}) if (ev) (void)hipEventDestroy(ev);
     (void)hipStreamDestroy(e->stream);
     delete e;
 }

@@ -1,21 +1,11 @@
 // zk_engine_enc.hip -- encode half of the batch engine (Level A of include/zeekstd_amd.h).
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include "../../include/zeekstd_amd.h"
 #include "zk_engine.h"
 #include "zk_kernels.h"
 #include "zk_enc_plan.h"
-
-#define ZK_HIP(call)                                                                                 \
-    do {                                                                                             \
-        hipError_t _e = (call);                                                                      \
-        if (_e != hipSuccess) {                                                                      \
-            e->last_err = std::string(#call) + ": " + hipGetErrorString(_e);                         \
-            return ZK_ERR_HIP;                                                                       \
-        }                                                                                            \
-    } while (0)
 
 // ---------------------------------------------------------------- predefined FSE compression tables (host, once)
 void zk_build_enc_tables(ZkEncTables *t)
@@ -48,156 +38,253 @@ extern "C" int zk_encode_frames_dev(zk_engine *e, const void *d_src, uint64_t n,
                                        n_frames_out, written_out, stream);
 }
 
-static int zk_pin_reserve(zk_engine *e, size_t bytes)
-{
-    if (bytes <= e->enc_pin_cap) return 0;
-    if (e->enc_pin) ZK_HIP(hipHostFree(e->enc_pin));
-    e->enc_pin = nullptr; e->enc_pin_cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    ZK_HIP(hipHostMalloc(&e->enc_pin, want, hipHostMallocDefault));
-    e->enc_pin_cap = want;
-    return 0;
-}
-
-// Enqueue one encode on `st`.  With dst_cap >= zk_compress_bound(n, frame_size) nothing blocks: the total size arrives in
-// the engine's pinned word ZK_HW_ENC_TOTAL once the stream has run (zk_encode_finish); a smaller destination needs the
-// total before the frames may be assembled, so the stream is synchronised once in the middle.
-// The frame / block lists are built in pinned host memory that stays untouched until the next enqueue: one encode in flight.
-int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32_t *nf_out)
-{
-    const uint64_t n = a.n;
-    const uint32_t frame_size = a.frame_size;
-    // the matcher sees the last `hist` bytes of the prefix right before every frame
-    const uint32_t hist = a.d_prefix ? zke_prefix_hist(a.prefix_len) : 0;
-    if (!e || frame_size == 0 || frame_size > ZK_SEEKABLE_MAX_FRAME_SIZE || !a.d_dst || (n && !a.d_src)) return ZK_ERR_ARGUMENT;
-    const uint64_t nf64 = n == 0 ? 1 : (n + frame_size - 1) / frame_size;
-    if (nf64 > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
-    ZK_HIP(hipSetDevice(e->device));
-
-    // frame / block / segment lists (host arithmetic only: zk_enc_plan.h)
+// ---------------------------------------------------------------- one encode: where everything lies
+// Filled by zk_enc_layout from the plan; the stages below read and write nothing of the engine's encode buffers but through it.
+namespace {
+struct ZkEncLayout {
     ZkEncPlan pl;
-    if (!zke_plan_count(n, frame_size, hist, &pl)) return -(int)ZK_E_GENERIC;
+    // pinned (zk_engine::Enc::pin), rounded to 64 bytes each: frames | blocks (+ 1) | doff | the predefined tables | segs
+    ZkEncFrame *frames; ZkEncBlock *blocks; uint64_t *doff; ZkEncTables *htab; ZkEncFrame *segs;
+    size_t frames_bytes;                    // of the frame list, rounded: the block list follows it on both sides, so one copy uploads both
+    // device twins: Enc::lists (frames | blocks), Enc::seg
+    ZkEncFrame *d_frames; ZkEncBlock *d_blocks; ZkEncFrame *d_segs;
+    // Enc::words: nf + 1 words each, then the predefined tables
+    uint64_t *c64, *out_off, *hashes, *d_doff; ZkEncTables *dtab;
+    uint64_t *seqs; uint32_t *mpos;         // Enc::seqs: seq_total + 1 packed sequences, the match positions behind them
+    uint8_t *lits, *scratch;                // Enc::lits, Enc::scratch
+    ZkEncTables *ftab;                      // Enc::ftab
+    // what the stages hand on
+    const uint8_t *src, *msrc;              // the input; what the matcher reads (prefix mode: the staged [prefix tail | frame] records)
+    ZkEncLdm ldm;                           // far history of this call (zk_enc_far_history)
+    size_t dense_span;                      // input bytes the dense scratch covers: a slice of whole frames, or all of it
+    uint32_t *cand, *part, *poff;           // Enc::dense: dense_span + ZKE_DENSE_SLACK candidates, as many sorted positions, the pass offsets
+    bool cks_beside;                        // the checksums run on the second queue and are joined before the assembly
+};
+template <class T> int zk_enc_reserve(zk_engine *e, zk_devbuf &b, size_t bytes, T **p)
+{
+    const int rc = zk_devbuf_reserve(e, b, bytes);
+    *p = (T *)b.p;
+    return rc;
+}
+}  // namespace
+
+// Counts come in with pl (zke_plan_count); the lists are filled in between the two halves, since the sequence and scratch totals
+// that size the device side come out of the fill.
+static int zk_enc_layout(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L)
+{
+    zk_engine::Enc &c = e->enc;
+    ZkEncPlan &pl = L.pl;
     const uint32_t nf = pl.nf, nb = pl.nb, nseg = pl.nseg;
     const size_t frames_bytes = ((size_t)nf * sizeof(ZkEncFrame) + 63) & ~(size_t)63;
     const size_t blocks_bytes = ((size_t)(nb + 1) * sizeof(ZkEncBlock) + 63) & ~(size_t)63;
     const size_t doff_bytes = ((size_t)(nf + 1) * 8 + 63) & ~(size_t)63;
     const size_t segs_bytes = ((size_t)(nseg + 1) * sizeof(ZkEncFrame) + 63) & ~(size_t)63;
+    const size_t segs_at = (frames_bytes + blocks_bytes + doff_bytes + sizeof(ZkEncTables) + 63) & ~(size_t)63;
     int rc;
-    if ((rc = zk_pin_reserve(e, frames_bytes + blocks_bytes + doff_bytes + sizeof(ZkEncTables) + 64 + segs_bytes))) return rc;
-    ZkEncFrame *frames = (ZkEncFrame *)e->enc_pin;
-    ZkEncBlock *blocks = (ZkEncBlock *)((uint8_t *)e->enc_pin + frames_bytes);
-    uint64_t *doff = (uint64_t *)((uint8_t *)e->enc_pin + frames_bytes + blocks_bytes);
-    ZkEncTables *htab = (ZkEncTables *)((uint8_t *)doff + doff_bytes);
-    ZkEncFrame *segs = (ZkEncFrame *)((uint8_t *)e->enc_pin + ((frames_bytes + blocks_bytes + doff_bytes + sizeof(ZkEncTables) + 63) & ~(size_t)63));
-    zke_plan_fill(n, frame_size, a.level, a.d_prefix ? a.prefix_len : 0, &pl, frames, blocks, segs, doff);
-    const uint64_t seq_total = pl.seq_total, scratch_total = pl.scratch_total;
-    if ((rc = zk_devbuf_reserve(e, e->enc_a, frames_bytes + blocks_bytes + 256))) return rc;
-    if ((rc = zk_devbuf_reserve(e, e->enc_b, (size_t)(seq_total + 1) * 12 + 64))) return rc;       // packed sequences (u64) + match positions (u32)
-    if ((rc = zk_devbuf_reserve(e, e->enc_c, (size_t)n + 64))) return rc;
-    if ((rc = zk_devbuf_reserve(e, e->enc_d, (size_t)scratch_total + 64))) return rc;
-    if ((rc = zk_devbuf_reserve(e, e->enc_e, (size_t)(nf + 1) * 8 * 4 + 64 + sizeof(ZkEncTables)))) return rc;   // c_size64, out_off, hashes, d_off, predefined tables
-    if ((rc = zk_devbuf_reserve(e, e->enc_f, (size_t)nf * sizeof(ZkEncTables) + 64))) return rc;                  // the frames' tables
-    ZkEncFrame *dfr = (ZkEncFrame *)e->enc_a.p;
-    ZkEncBlock *dbl = (ZkEncBlock *)((uint8_t *)e->enc_a.p + frames_bytes);
-    uint64_t *c64 = (uint64_t *)e->enc_e.p, *out_off = c64 + (nf + 1), *hashes = out_off + (nf + 1), *d_doff = hashes + (nf + 1);
-    ZkEncTables *dtab = (ZkEncTables *)(d_doff + (nf + 1));
-    if (!e->enc_tables_ready) { zk_build_enc_tables(&e->enc_tables); e->enc_tables_ready = true; }
-    *htab = e->enc_tables;
-    ZK_HIP(hipMemcpyAsync(dfr, frames, frames_bytes + (size_t)nb * sizeof(ZkEncBlock), hipMemcpyHostToDevice, st));   // frames + blocks are contiguous
-    ZK_HIP(hipMemcpyAsync(d_doff, doff, (size_t)(nf + 1) * 8, hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemcpyAsync(dtab, htab, sizeof(ZkEncTables), hipMemcpyHostToDevice, st));
+    if ((rc = zk_pin_reserve(e, c.pin, c.pin_cap, frames_bytes + blocks_bytes + doff_bytes + sizeof(ZkEncTables) + 64 + segs_bytes))) return rc;
+    L.frames_bytes = frames_bytes;
+    L.frames = (ZkEncFrame *)c.pin;
+    L.blocks = (ZkEncBlock *)(c.pin + frames_bytes);
+    L.doff = (uint64_t *)(c.pin + frames_bytes + blocks_bytes);
+    L.htab = (ZkEncTables *)(c.pin + frames_bytes + blocks_bytes + doff_bytes);
+    L.segs = (ZkEncFrame *)(c.pin + segs_at);
+    zke_plan_fill(a.n, a.frame_size, a.level, a.d_prefix ? a.prefix_len : 0, &pl, L.frames, L.blocks, L.segs, L.doff);
+    uint8_t *lists;
+    if ((rc = zk_enc_reserve(e, c.lists, frames_bytes + blocks_bytes + 256, &lists))) return rc;
+    if ((rc = zk_enc_reserve(e, c.seqs, (size_t)(pl.seq_total + 1) * 12 + 64, &L.seqs))) return rc;       // packed sequences (u64) + match positions (u32)
+    if ((rc = zk_enc_reserve(e, c.lits, (size_t)a.n + 64, &L.lits))) return rc;
+    if ((rc = zk_enc_reserve(e, c.scratch, (size_t)pl.scratch_total + 64, &L.scratch))) return rc;
+    if ((rc = zk_enc_reserve(e, c.words, (size_t)(nf + 1) * 8 * 4 + 64 + sizeof(ZkEncTables), &L.c64))) return rc;
+    if ((rc = zk_enc_reserve(e, c.ftab, (size_t)nf * sizeof(ZkEncTables) + 64, &L.ftab))) return rc;
+    if ((rc = zk_enc_reserve(e, c.seg, segs_bytes + 64, &L.d_segs))) return rc;
+    L.d_frames = (ZkEncFrame *)lists;
+    L.d_blocks = (ZkEncBlock *)(lists + frames_bytes);
+    L.mpos = (uint32_t *)(L.seqs + pl.seq_total + 1);
+    L.out_off = L.c64 + (nf + 1); L.hashes = L.out_off + (nf + 1); L.d_doff = L.hashes + (nf + 1);
+    L.dtab = (ZkEncTables *)(L.d_doff + (nf + 1));
+    return 0;
+}
+
+// ---------------------------------------------------------------- the stages of an encode, in the order zk_encode_enqueue runs them
+// frame / block / segment lists (host arithmetic only: zk_enc_plan.h), then lists, frame offsets and predefined tables go up
+static int zk_enc_plan_upload(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
+{
+    // the matcher sees the last `hist` bytes of the prefix right before every frame
+    if (!zke_plan_count(a.n, a.frame_size, a.d_prefix ? zke_prefix_hist(a.prefix_len) : 0, &L.pl)) return -(int)ZK_E_GENERIC;
+    int rc;
+    if ((rc = zk_enc_layout(e, a, L))) return rc;
+    if (!e->enc.tables_ready) { zk_build_enc_tables(&e->enc.tables); e->enc.tables_ready = true; }
+    *L.htab = e->enc.tables;
+    ZK_HIP(hipMemcpyAsync(L.d_frames, L.frames, L.frames_bytes + (size_t)L.pl.nb * sizeof(ZkEncBlock), hipMemcpyHostToDevice, st));   // frames + blocks are contiguous
+    ZK_HIP(hipMemcpyAsync(L.d_doff, L.doff, (size_t)(L.pl.nf + 1) * 8, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(L.dtab, L.htab, sizeof(ZkEncTables), hipMemcpyHostToDevice, st));
     zk_profile_begin(e);
-    const uint8_t *src = (const uint8_t *)a.d_src;
-    const uint8_t *msrc = src;                               // what the matcher reads
+    L.src = L.msrc = (const uint8_t *)a.d_src;
+    return 0;
+}
+
+// prefix mode: [prefix tail | frame] records for the matcher; and the records its workgroups are launched over, the segments
+// (one per <= 256 KiB of a frame)
+static int zk_enc_stage_hist(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
+{
+    const uint32_t hist = L.pl.hist;
     if (hist) {
-        if ((rc = zk_devbuf_reserve(e, e->enc_hist, (size_t)nf * ((size_t)hist + frame_size) + 64))) return rc;
-        zk_launch_enc_stage_hist(st, src, (const uint8_t *)a.d_prefix + (a.prefix_len - hist), dfr, nf, (uint8_t *)e->enc_hist.p);
-        msrc = (const uint8_t *)e->enc_hist.p;
+        uint8_t *stage;
+        int rc;
+        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)L.pl.nf * ((size_t)hist + a.frame_size) + 64, &stage))) return rc;
+        zk_launch_enc_stage_hist(st, L.src, (const uint8_t *)a.d_prefix + (a.prefix_len - hist), L.d_frames, L.pl.nf, stage);
+        L.msrc = stage;
     }
-    // a prefix the ring cannot hold: its sampled positions enter a table in HBM (rebuilt per call: the bytes are the caller's)
-    ZkEncLdm ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0};
-    // the matcher's workgroups are launched over the segments (one per <= 256 KiB of a frame)
-    if ((rc = zk_devbuf_reserve(e, e->enc_seg, segs_bytes + 64))) return rc;
-    ZK_HIP(hipMemcpyAsync(e->enc_seg.p, segs, (size_t)nseg * sizeof(ZkEncFrame), hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(L.d_segs, L.segs, (size_t)L.pl.nseg * sizeof(ZkEncFrame), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// far history (ZkEncLdm), one of: none; a table per frame over its own bytes, with the dense candidates on top at the dense
+// levels; a table over a prefix the ring cannot hold (rebuilt per call: the bytes are the caller's)
+static int zk_enc_far_history(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
+{
+    const uint32_t frame_size = a.frame_size, nf = L.pl.nf;
+    ZkEncLdm &ldm = L.ldm;
+    ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0};
+    L.dense_span = 0;
+    int rc;
+    uint32_t *table;
     // (a prefix of one to three bytes leaves no history -- hist is a multiple of 4 -- but it is a prefix: the frames' windows were planned without
     //  far history, as the twin does; found by reading, round 6: such a frame would have carried offsets beyond its window)
-    const uint64_t plen_eff = a.d_prefix ? a.prefix_len : 0;
-    uint64_t dense_slice = 4ull << 30;
-    if (const char *v = getenv("ZK_DENSE_SLICE_BYTES")) { const unsigned long long x = strtoull(v, nullptr, 10); if (x) dense_slice = x; }
-    size_t dense_span = 0;
-    if (!hist && zke_ldm_in_frame(a.level, plen_eff, frame_size < a.n ? frame_size : a.n)) {
+    const uint64_t plen_eff = a.d_prefix ? a.prefix_len : 0, frame_max = frame_size < a.n ? frame_size : a.n;
+    if (!L.pl.hist && zke_ldm_in_frame(a.level, plen_eff, frame_max)) {
         // in-frame far history (level >= 2, no prefix, frames beyond the ring's reach): one table per frame over its own bytes
-        ldm.inframe = 1; ldm.frame_size = frame_size; ldm.n_total = a.n; ldm.log = zke_ldm_log(frame_size < a.n ? frame_size : a.n);
-        if ((rc = zk_devbuf_reserve(e, e->enc_ldm, (((size_t)nf * sizeof(uint32_t)) << ldm.log) + 64))) return rc;
-        if (zk_launch_enc_ldm_build_frames(st, src, ldm, (uint32_t *)e->enc_ldm.p, nf)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
-        ldm.table = (const uint32_t *)e->enc_ldm.p;
-        if (zke_dense_in_frame(a.level, plen_eff, frame_size < a.n ? frame_size : a.n)) {
+        ldm.inframe = 1; ldm.frame_size = frame_size; ldm.n_total = a.n; ldm.log = zke_ldm_log(frame_max);
+        if ((rc = zk_enc_reserve(e, e->enc.ldm, (((size_t)nf * sizeof(uint32_t)) << ldm.log) + 64, &table))) return rc;
+        if (zk_launch_enc_ldm_build_frames(st, L.src, ldm, table, nf)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
+        ldm.table = table;
+        if (zke_dense_in_frame(a.level, plen_eff, frame_max)) {
             // dense far history (level 0 / >= 3): a far candidate per input byte, 4 bytes each (with the sorted positions 8 x the input: HBM is what this device has)
             ldm.dlog = zke_dense_log(a.level);
             // + as much again for the positions sorted by the pass their slot belongs to, and a word per segment and pass (+ 1)
-            // -- for a SLICE of whole frames at a time (at most dense_slice bytes of input: 4 GiB unless ZK_DENSE_SLICE_BYTES says otherwise, which
-            // the tests use): the dense kernels and the match kernel run slice after slice over the same scratch, so a call of any size takes at
-            // most 8 x 4 GiB of it
-            dense_span = (size_t)(n < dense_slice ? n : (dense_slice / frame_size ? dense_slice / frame_size : 1) * (uint64_t)frame_size);
-            if ((rc = zk_devbuf_reserve(e, e->enc_dense, (2 * (dense_span + ZKE_DENSE_SLACK) + (size_t)nseg * (ZKE_DENSE_PASSES_MAX + 1)) * sizeof(uint32_t) + 64))) return rc;
-            ldm.dense = (const uint32_t *)e->enc_dense.p;
+            // -- for a SLICE of whole frames at a time (at most dense_slice bytes of input: 4 GiB unless ZK_CHOICE_ENC_DENSE_SLICE_KIB says
+            // otherwise, which the tests use): the dense kernels and the match kernel run slice after slice over the same scratch, so a call
+            // of any size takes at most 8 x 4 GiB of it
+            const uint64_t dense_slice = e->enc.dense_slice_bytes ? e->enc.dense_slice_bytes : 4ull << 30;
+            L.dense_span = (size_t)(a.n < dense_slice ? a.n : (dense_slice / frame_size ? dense_slice / frame_size : 1) * (uint64_t)frame_size);
+            if ((rc = zk_enc_reserve(e, e->enc.dense, (2 * (L.dense_span + ZKE_DENSE_SLACK) + (size_t)L.pl.nseg * (ZKE_DENSE_PASSES_MAX + 1)) * sizeof(uint32_t) + 64, &L.cand))) return rc;
+            L.part = L.cand + (L.dense_span + ZKE_DENSE_SLACK); L.poff = L.part + (L.dense_span + ZKE_DENSE_SLACK);
+            ldm.dense = L.cand;
         }
     }
-    if (hist && a.prefix_len > ZKE_WINDOW) {
+    if (L.pl.hist && a.prefix_len > ZKE_WINDOW) {
         const uint64_t usable = zke_ldm_usable(a.prefix_len);
         ldm.pfx = (const uint8_t *)a.d_prefix; ldm.plen = a.prefix_len; ldm.u0 = a.prefix_len - usable; ldm.log = zke_ldm_log(usable);
-        if ((rc = zk_devbuf_reserve(e, e->enc_ldm, (sizeof(uint32_t) << ldm.log) + 64))) return rc;
-        if (zk_launch_enc_ldm_build(st, ldm, (uint32_t *)e->enc_ldm.p)) { e->last_err = "hipMemsetAsync (long-distance table)"; return ZK_ERR_HIP; }
-        ldm.table = (const uint32_t *)e->enc_ldm.p;
+        if ((rc = zk_enc_reserve(e, e->enc.ldm, (sizeof(uint32_t) << ldm.log) + 64, &table))) return rc;
+        if (zk_launch_enc_ldm_build(st, ldm, table)) { e->last_err = "hipMemsetAsync (long-distance table)"; return ZK_ERR_HIP; }
+        ldm.table = table;
     }
-    if (ldm.dense && dense_span < n) {
-        // slice after slice (whole frames): the candidate arrays are indexed like the source, so a slice's kernels get them shifted by
-        // the slice's first byte; the timer of the match kernel covers the dense kernels of such a call too
-        zk_kernel_timer t(e, ZK_K_ENC_MATCH, st);
-        uint32_t *dc = (uint32_t *)e->enc_dense.p, *dp = dc + (dense_span + ZKE_DENSE_SLACK), *po = dp + (dense_span + ZKE_DENSE_SLACK);
-        const uint32_t fpf = (uint32_t)(dense_span / frame_size), spf = (frame_size + ZKE_SEGMENT - 1) / ZKE_SEGMENT;   // frames per slice, segments per whole frame
-        for (uint32_t f0 = 0; f0 < nf; f0 += fpf) {
-            const uint32_t f1 = nf - f0 < fpf ? nf : f0 + fpf, s0 = f0 * spf, s1 = f1 == nf ? nseg : f1 * spf;
-            const uint64_t lo = (uint64_t)f0 * frame_size;
-            ZkEncLdm sl = ldm;
-            sl.dense = dc - lo;
-            const ZkEncFrame *sg = (const ZkEncFrame *)e->enc_seg.p + s0;
-            zk_launch_enc_dense_cand(st, src, sg, s1 - s0, sl, dc - lo, dp - lo, po);
-            zk_launch_enc_match(st, msrc, sg, s1 - s0, dbl, (uint64_t *)e->enc_b.p, (uint8_t *)e->enc_c.p, a.level, sl);
+    return 0;
+}
+
+// the match pass, slice after slice of whole frames: the dense candidates of a slice, then the matcher over its segments.  Without
+// dense history, or when its scratch spans the whole input, everything is one slice.  The candidate arrays are indexed like the
+// source, so a slice's kernels get them shifted by the slice's first byte.  Timed: the two kernels of one slice each by itself;
+// of several, the whole loop as the match kernel.
+static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
+{
+    const uint32_t nf = L.pl.nf, nseg = L.pl.nseg, frame_size = a.frame_size;
+    const bool sliced = L.ldm.dense && L.dense_span < a.n;
+    const uint32_t fpf = sliced ? (uint32_t)(L.dense_span / frame_size) : nf, spf = (frame_size + ZKE_SEGMENT - 1) / ZKE_SEGMENT;   // frames per slice, segments per whole frame
+    zk_kernel_timer whole(e, ZK_K_ENC_MATCH, st, sliced);
+    for (uint32_t f0 = 0; f0 < nf; f0 += fpf) {
+        const uint32_t f1 = nf - f0 < fpf ? nf : f0 + fpf, s0 = f0 * spf, s1 = f1 == nf ? nseg : f1 * spf;
+        const uint64_t lo = (uint64_t)f0 * frame_size;
+        ZkEncLdm sl = L.ldm;
+        if (sl.dense) {
+            sl.dense = L.cand - lo;
+            zk_kernel_timer t(e, ZK_K_ENC_DENSE, st, !sliced);
+            zk_launch_enc_dense_cand(st, L.src, L.d_segs + s0, s1 - s0, sl, L.cand - lo, L.part - lo, L.poff);
         }
-    } else {
-        if (ldm.dense) { zk_kernel_timer t(e, ZK_K_ENC_DENSE, st); uint32_t *dc = (uint32_t *)e->enc_dense.p, *dp = dc + (dense_span + ZKE_DENSE_SLACK);
-                         zk_launch_enc_dense_cand(st, src, (const ZkEncFrame *)e->enc_seg.p, nseg, ldm, dc, dp, dp + (dense_span + ZKE_DENSE_SLACK)); }
-        { zk_kernel_timer t(e, ZK_K_ENC_MATCH, st); zk_launch_enc_match(st, msrc, (const ZkEncFrame *)e->enc_seg.p, nseg, dbl, (uint64_t *)e->enc_b.p, (uint8_t *)e->enc_c.p, a.level, ldm); }
+        zk_kernel_timer t(e, ZK_K_ENC_MATCH, st, !sliced);
+        zk_launch_enc_match(st, L.msrc, L.d_segs + s0, s1 - s0, L.d_blocks, L.seqs, L.lits, a.level, sl);
     }
-    ZkEncTables *ftab = (ZkEncTables *)e->enc_f.p;
-    { zk_kernel_timer t(e, ZK_K_ENC_FSE_BUILD, st); zk_launch_enc_fse_build(st, src, dfr, nf, dbl, (uint64_t *)e->enc_b.p, (uint32_t *)((uint64_t *)e->enc_b.p + seq_total + 1), dtab, ftab); }
-    bool cks_beside = false;                                 // the checksums run on the second queue beside the entropy stage (which waits on its own chains; beside the matcher they
-                                                             // cost it 2 ms of vector issue slots) and are joined before the assembly
-    if (a.checksum) {
-        if (!e->profiling && !e->enc_aux) {
-            if (hipStreamCreateWithFlags(&e->enc_aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e->enc_ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&e->enc_ev_join, hipEventDisableTiming) != hipSuccess) { e->enc_aux = nullptr; (void)hipGetLastError(); }
-        }
-        if (!e->profiling && e->enc_aux) {
-            ZK_HIP(hipEventRecord(e->enc_ev_fork, st));
-            ZK_HIP(hipStreamWaitEvent(e->enc_aux, e->enc_ev_fork, 0));
-            zk_launch_xxh64(e->enc_aux, src, d_doff, 0, nf, nullptr, hashes, e->choice, nullptr, 512, true);
-            ZK_HIP(hipEventRecord(e->enc_ev_join, e->enc_aux));
-            cks_beside = true;
-        } else { zk_kernel_timer t(e, ZK_K_ENC_XXH64, st); zk_launch_xxh64(st, src, d_doff, 0, nf, nullptr, hashes, e->choice, nullptr, 512, true); }
+    return 0;
+}
+
+// the frames' FSE tables from their sequences
+static int zk_enc_table_build(zk_engine *e, const zk_enc_args &, ZkEncLayout &L, hipStream_t st)
+{
+    zk_kernel_timer t(e, ZK_K_ENC_FSE_BUILD, st);
+    zk_launch_enc_fse_build(st, L.src, L.d_frames, L.pl.nf, L.d_blocks, L.seqs, L.mpos, L.dtab, L.ftab);
+    return 0;
+}
+
+// the checksums: on the second queue beside the entropy stage (which waits on its own chains; beside the matcher they cost it
+// 2 ms of vector issue slots), joined by zk_enc_assemble; on st when profiling, or when the second queue cannot be had
+static int zk_enc_checksums_fork(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
+{
+    zk_engine::Enc &c = e->enc;
+    L.cks_beside = false;
+    if (!a.checksum) return 0;
+    if (!e->profiling && !c.aux) {
+        if (hipStreamCreateWithFlags(&c.aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming) != hipSuccess) { c.aux = nullptr; (void)hipGetLastError(); }
     }
-    { zk_kernel_timer t(e, ZK_K_ENC_ENTROPY, st); zk_launch_enc_entropy(st, src, dfr, dbl, nb, (uint64_t *)e->enc_b.p, (uint32_t *)((uint64_t *)e->enc_b.p + seq_total + 1), (const uint8_t *)e->enc_c.p, (uint8_t *)e->enc_d.p, ftab); }
-    zk_launch_enc_sizes(st, dfr, nf, dbl, ftab, a.checksum, c64, (uint32_t *)a.d_c_sizes, (uint32_t *)a.d_d_sizes);
-    zk_launch_scan64(st, c64, nf, out_off);
-    ZK_HIP(hipMemcpyAsync(e->h_words + ZK_HW_ENC_TOTAL, out_off + nf, 8, hipMemcpyDeviceToHost, st));
-    if (a.dst_cap < zk_compress_bound(n, frame_size)) {      // the frames may not fit: the total decides before anything is written
-        ZK_HIP(hipStreamSynchronize(st));
-        if (e->h_words[ZK_HW_ENC_TOTAL] > a.dst_cap) return -(int)ZK_E_DST_TOO_SMALL;
-    }
-    if (cks_beside) ZK_HIP(hipStreamWaitEvent(st, e->enc_ev_join, 0));
-    { zk_kernel_timer t(e, ZK_K_ENC_COMPACT, st); zk_launch_enc_assemble(st, src, dfr, nf, dbl, nb, ftab, (const uint8_t *)e->enc_c.p, (const uint8_t *)e->enc_d.p, out_off, c64, hashes, a.checksum, (uint8_t *)a.d_dst); }
-    if (nf_out) *nf_out = nf;
+    if (!e->profiling && c.aux) {
+        ZK_HIP(hipEventRecord(c.ev_fork, st));
+        ZK_HIP(hipStreamWaitEvent(c.aux, c.ev_fork, 0));
+        zk_launch_xxh64(c.aux, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, e->choice, nullptr, 512, true);
+        ZK_HIP(hipEventRecord(c.ev_join, c.aux));
+        L.cks_beside = true;
+    } else { zk_kernel_timer t(e, ZK_K_ENC_XXH64, st); zk_launch_xxh64(st, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, e->choice, nullptr, 512, true); }
+    return 0;
+}
+
+static int zk_enc_entropy(zk_engine *e, const zk_enc_args &, ZkEncLayout &L, hipStream_t st)
+{
+    zk_kernel_timer t(e, ZK_K_ENC_ENTROPY, st);
+    zk_launch_enc_entropy(st, L.src, L.d_frames, L.d_blocks, L.pl.nb, L.seqs, L.mpos, L.lits, L.scratch, L.ftab);
+    return 0;
+}
+
+// frame sizes (the caller's seek entries too), their prefix sums, and the total on its way to the pinned word ZK_HW_ENC_TOTAL
+static int zk_enc_sizes_total(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
+{
+    const uint32_t nf = L.pl.nf;
+    zk_launch_enc_sizes(st, L.d_frames, nf, L.d_blocks, L.ftab, a.checksum, L.c64, (uint32_t *)a.d_c_sizes, (uint32_t *)a.d_d_sizes);
+    zk_launch_scan64(st, L.c64, nf, L.out_off);
+    ZK_HIP(hipMemcpyAsync(e->h_words + ZK_HW_ENC_TOTAL, L.out_off + nf, 8, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// a destination below the bound: the frames may not fit, and the total decides before anything is written
+static int zk_enc_fit_check(zk_engine *e, const zk_enc_args &a, ZkEncLayout &, hipStream_t st)
+{
+    if (a.dst_cap >= zk_compress_bound(a.n, a.frame_size)) return 0;
+    ZK_HIP(hipStreamSynchronize(st));
+    return e->h_words[ZK_HW_ENC_TOTAL] > a.dst_cap ? -(int)ZK_E_DST_TOO_SMALL : 0;
+}
+
+// the checksums join, then the frames are put together at their offsets
+static int zk_enc_assemble(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
+{
+    if (L.cks_beside) ZK_HIP(hipStreamWaitEvent(st, e->enc.ev_join, 0));
+    zk_kernel_timer t(e, ZK_K_ENC_COMPACT, st);
+    zk_launch_enc_assemble(st, L.src, L.d_frames, L.pl.nf, L.d_blocks, L.pl.nb, L.ftab, L.lits, L.scratch, L.out_off, L.c64, L.hashes, a.checksum, (uint8_t *)a.d_dst);
+    return 0;
+}
+
+// Enqueue one encode on `st`.  With dst_cap >= zk_compress_bound(n, frame_size) nothing blocks: the total size arrives in
+// the engine's pinned word ZK_HW_ENC_TOTAL once the stream has run (zk_encode_finish); a smaller destination needs the
+// total before the frames may be assembled, so the stream is synchronised once in the middle (zk_enc_fit_check).
+// The frame / block lists are built in pinned host memory that stays untouched until the next enqueue: one encode in flight.
+int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32_t *nf_out)
+{
+    if (!e || a.frame_size == 0 || a.frame_size > ZK_SEEKABLE_MAX_FRAME_SIZE || !a.d_dst || (a.n && !a.d_src)) return ZK_ERR_ARGUMENT;
+    if ((a.n == 0 ? 1 : (a.n + a.frame_size - 1) / a.frame_size) > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
+    ZK_HIP(hipSetDevice(e->device));
+    static int (*const stages[])(zk_engine *, const zk_enc_args &, ZkEncLayout &, hipStream_t) = {
+        zk_enc_plan_upload, zk_enc_stage_hist, zk_enc_far_history, zk_enc_match, zk_enc_table_build, zk_enc_checksums_fork,
+        zk_enc_entropy, zk_enc_sizes_total, zk_enc_fit_check, zk_enc_assemble};
+    ZkEncLayout L;
+    for (auto stage : stages) if (const int rc = stage(e, a, L, st)) return rc;
+    if (nf_out) *nf_out = L.pl.nf;
     return 0;
 }
 

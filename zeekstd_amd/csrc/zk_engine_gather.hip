@@ -20,15 +20,6 @@
 #include "zk_engine.h"
 #include "host/zeekstd.hpp"
 
-#define ZK_HIP(call)                                                                                 \
-    do {                                                                                             \
-        hipError_t _e = (call);                                                                      \
-        if (_e != hipSuccess) {                                                                      \
-            e->last_err = std::string(#call) + ": " + hipGetErrorString(_e);                         \
-            return ZK_ERR_HIP;                                                                       \
-        }                                                                                            \
-    } while (0)
-
 namespace {
 typedef int (*allgather_fn)(const void *, void *, size_t, int, void *, hipStream_t);
 typedef int (*sendrecv_fn)(void *, size_t, int, int, void *, hipStream_t);

@@ -28,15 +28,6 @@
 #include "zk_engine.h"
 #include "zk_kernels.h"
 
-#define ZK_HIP(call)                                                                                 \
-    do {                                                                                             \
-        hipError_t _e = (call);                                                                      \
-        if (_e != hipSuccess) {                                                                      \
-            e->last_err = std::string(#call) + ": " + hipGetErrorString(_e);                         \
-            return ZK_ERR_HIP;                                                                       \
-        }                                                                                            \
-    } while (0)
-
 // ---------------------------------------------------------------------------------------------- worker threads
 namespace {
 
@@ -224,29 +215,18 @@ struct zk_hostpipe {
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     ZkRing ring_in, ring_out;                    // allocated on the first large call
     bool rings_ready = false;
+    // HBM buffers of one chunk in flight: its input, its output, its offsets (decode) or seek entries (encode), its status words (decode)
     struct Slot {
-        zk_devbuf d_in, d_out, d_off, d_st;
-        hipEvent_t ev_in = nullptr, ev_dec = nullptr, ev_out = nullptr;
+        zk_devbuf in, out, meta, st;
+        hipEvent_t ev_in = nullptr, ev_run = nullptr, ev_out = nullptr;     // upload done, kernels done, download done
         bool out_pending = false;                // ev_out was recorded for an earlier chunk
-    } slot[NS];
+    } slot[NS], es[2];                           // decode: a chunk per context + 1; encode: double-buffered
+    Slot &any_slot(int i) { return i < NS ? slot[i] : es[i - NS]; }
     // small pinned areas: offsets / status words of the call in flight, and the staging of small requests
     uint8_t *pin_meta = nullptr; size_t pin_meta_cap = 0;
     uint8_t *pin_small = nullptr; size_t pin_small_cap = 0;
     uint32_t *pin_flag = nullptr; uint32_t small_gen = 0;      // completion word of the small path, written by its last kernel
-    // encode: double-buffered HBM chunk buffers
-    struct ESlot { zk_devbuf d_src, d_dst, d_sizes; hipEvent_t ev_in = nullptr, ev_enc = nullptr, ev_out = nullptr; bool out_pending = false; } es[2];
 };
-
-static int zk_pin_grow(zk_engine *e, uint8_t *&p, size_t &cap, size_t bytes)
-{
-    if (bytes <= cap) return 0;
-    if (p) ZK_HIP(hipHostFree(p));
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 2 + 4096;
-    ZK_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-    cap = want;
-    return 0;
-}
 
 static int zk_hostpipe_get(zk_engine *e, zk_hostpipe **out)
 {
@@ -263,18 +243,14 @@ static int zk_hostpipe_get(zk_engine *e, zk_hostpipe **out)
     e->hp = hp;
     ZK_HIP(hipStreamCreateWithFlags(&hp->s_h2d, hipStreamNonBlocking));
     ZK_HIP(hipStreamCreateWithFlags(&hp->s_d2h, hipStreamNonBlocking));
-    for (auto &s : hp->slot) {
+    for (int i = 0; i < zk_hostpipe::NS + 2; i++) {
+        zk_hostpipe::Slot &s = hp->any_slot(i);
         ZK_HIP(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-        ZK_HIP(hipEventCreateWithFlags(&s.ev_dec, hipEventDisableTiming));
+        ZK_HIP(hipEventCreateWithFlags(&s.ev_run, hipEventDisableTiming));
         ZK_HIP(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
     }
     ZK_HIP(hipHostMalloc((void **)&hp->pin_flag, 64, hipHostMallocDefault));
     *hp->pin_flag = 0;
-    for (auto &s : hp->es) {
-        ZK_HIP(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-        ZK_HIP(hipEventCreateWithFlags(&s.ev_enc, hipEventDisableTiming));
-        ZK_HIP(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
-    }
     *out = hp;
     return 0;
 }
@@ -306,13 +282,10 @@ void zk_hostpipe_destroy(zk_engine *e)
     if (hp->s_d2h) (void)hipStreamSynchronize(hp->s_d2h);
     delete hp->pool;
     hp->ring_in.destroy(); hp->ring_out.destroy();
-    for (auto &s : hp->slot) {
-        for (zk_devbuf *b : {&s.d_in, &s.d_out, &s.d_off, &s.d_st}) if (b->p) (void)hipFree(b->p);
-        for (hipEvent_t ev : {s.ev_in, s.ev_dec, s.ev_out}) if (ev) (void)hipEventDestroy(ev);
-    }
-    for (auto &s : hp->es) {
-        for (zk_devbuf *b : {&s.d_src, &s.d_dst, &s.d_sizes}) if (b->p) (void)hipFree(b->p);
-        for (hipEvent_t ev : {s.ev_in, s.ev_enc, s.ev_out}) if (ev) (void)hipEventDestroy(ev);
+    for (int i = 0; i < zk_hostpipe::NS + 2; i++) {
+        zk_hostpipe::Slot &s = hp->any_slot(i);
+        for (zk_devbuf *b : {&s.in, &s.out, &s.meta, &s.st}) if (b->p) (void)hipFree(b->p);
+        for (hipEvent_t ev : {s.ev_in, s.ev_run, s.ev_out}) if (ev) (void)hipEventDestroy(ev);
     }
     if (hp->pin_meta) (void)hipHostFree(hp->pin_meta);
     if (hp->pin_small) (void)hipHostFree(hp->pin_small);
@@ -394,6 +367,63 @@ static int zk_src_fill(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src, ui
     return 0;
 }
 
+// Uploads n bytes of the source at payload offset `off` to d_dst, on the upload queue.  By what the caller found out about the
+// source: memory that is pinned already goes by DMA as it is; a small request is staged through pin_small by this thread; the
+// rest goes unit by unit straight from the caller's pages where `win` could pin them, and through ring_in (created on first
+// use; a piece is free again once the event behind its copy has passed) where it could not or the source is a callback.
+static int zk_pipe_upload(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src, uint64_t off, uint8_t *d_dst, uint64_t n, bool src_pinned, bool small,
+                          ZkRegWindow &win)
+{
+    int r;
+    if (src_pinned) {
+        if (n) ZK_HIP(hipMemcpyAsync(d_dst, src.mem + off, n, hipMemcpyHostToDevice, hp->s_h2d));
+    } else if (small) {
+        if ((r = zk_src_fill(e, hp, src, off, hp->pin_small, (size_t)n))) return r;
+        if (n) ZK_HIP(hipMemcpyAsync(d_dst, hp->pin_small, n, hipMemcpyHostToDevice, hp->s_h2d));
+    } else {
+        for (uint64_t at = 0; at < n;) {
+            if (src.mem && win.ok(src.mem + off + at)) {
+                const size_t sp = win.span(src.mem + off + at), len = (size_t)(n - at < sp ? n - at : sp);
+                ZK_HIP(hipMemcpyAsync(d_dst + at, src.mem + off + at, len, hipMemcpyHostToDevice, hp->s_h2d));
+                at += len;
+                continue;
+            }
+            if ((r = zk_hostpipe_rings(e, hp))) return r;
+            const size_t len = (size_t)(n - at < zk_hostpipe::PIECE ? n - at : zk_hostpipe::PIECE);
+            ZkRing::Piece &pc = hp->ring_in.pc[hp->ring_in.acquire()];
+            if ((r = zk_src_fill(e, hp, src, off + at, pc.p, len))) return r;
+            ZK_HIP(hipMemcpyAsync(d_dst + at, pc.p, len, hipMemcpyHostToDevice, hp->s_h2d));
+            ZK_HIP(hipEventRecord(pc.ev, hp->s_h2d));
+            pc.ev_pending = true;
+            at += len;
+        }
+    }
+    return 0;
+}
+
+// One ring piece's way down: n bytes at d_src into the next piece of ring_out on the download queue, the piece's event behind
+// them.  The piece is held until its consumer releases it.  Returns the piece's index, or an error (< 0).
+static int zk_pipe_download_piece(zk_engine *e, zk_hostpipe *hp, const uint8_t *d_src, size_t n)
+{
+    const int k = hp->ring_out.acquire();
+    ZkRing::Piece &pc = hp->ring_out.pc[k];
+    ZK_HIP(hipMemcpyAsync(pc.p, d_src, n, hipMemcpyDeviceToHost, hp->s_d2h));
+    ZK_HIP(hipEventRecord(pc.ev, hp->s_d2h));
+    hp->ring_out.hold(k);
+    return k;
+}
+
+// The verdict of a decode from its frames' status words: the leading frames that are fine, the caller's copy of the words, and
+// the return code (0, or the first failure).
+static int zk_frames_verdict(const int32_t *status, uint32_t count, int32_t *frame_status, uint32_t *n_ok)
+{
+    uint32_t ok = count;
+    for (uint32_t i = 0; i < count; i++) if (status[i] != 0) { ok = i; break; }
+    if (frame_status) memcpy(frame_status, status, (size_t)count * 4);
+    if (n_ok) *n_ok = ok;
+    return ok == count ? 0 : -(int)status[ok];
+}
+
 // ---------------------------------------------------------------------------------------------- decode: the small path
 // A seek (one frame, a few): four or five kernel launches on one queue, no copy command, no read-back in the middle, and
 // the host spins on a pinned completion word instead of a stream synchronisation.  See zk_decode.hip (zk_k_small_*).
@@ -410,7 +440,7 @@ static int zk_decode_small(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src
     const size_t offs_bytes = ((size_t)(count + 1) * 16 + 63) & ~(size_t)63;
     const size_t comp_bytes = ((size_t)csz + 15 + 64) & ~(size_t)63;
     const size_t stat_bytes = ((size_t)count * 4 + 63) & ~(size_t)63;
-    if ((rc = zk_pin_grow(e, hp->pin_small, hp->pin_small_cap, offs_bytes + comp_bytes + stat_bytes + (dst_pinned ? 0 : (size_t)dsz + 64)))) return rc;
+    if ((rc = zk_pin_reserve(e, hp->pin_small, hp->pin_small_cap, offs_bytes + comp_bytes + stat_bytes + (dst_pinned ? 0 : (size_t)dsz + 64)))) return rc;
     uint64_t *h_offs = (uint64_t *)hp->pin_small;
     uint8_t *h_comp = hp->pin_small + offs_bytes;
     int32_t *h_status = (int32_t *)(h_comp + comp_bytes);
@@ -429,17 +459,17 @@ static int zk_decode_small(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src
     const uint64_t seq_cap = dsz / 3 + count + 1 + 8ull * (block_cap + 1);        // record slots: what the walk may hand out (it checks)
     if ((rc = zk_devbuf_reserve(e, c.seqs, (size_t)seq_cap * sizeof(ZkSeqP)))) return rc;     // (+ 7 per block: a block's records start on a 64-byte line)
     if ((rc = zk_devbuf_reserve(e, c.lit, (size_t)dsz + 64))) return rc;
-    if ((rc = zk_devbuf_reserve(e, s.d_in, comp_bytes + 64))) return rc;
-    if ((rc = zk_devbuf_reserve(e, s.d_out, (size_t)dsz + 64))) return rc;
-    if ((rc = zk_devbuf_reserve(e, s.d_off, offs_bytes))) return rc;
-    if ((rc = zk_devbuf_reserve(e, s.d_st, stat_bytes))) return rc;
+    if ((rc = zk_devbuf_reserve(e, s.in, comp_bytes + 64))) return rc;
+    if ((rc = zk_devbuf_reserve(e, s.out, (size_t)dsz + 64))) return rc;
+    if ((rc = zk_devbuf_reserve(e, s.meta, offs_bytes))) return rc;
+    if ((rc = zk_devbuf_reserve(e, s.st, stat_bytes))) return rc;
     hipStream_t st = c.st;
     ZkFrameInfo *infos = (ZkFrameInfo *)c.infos.p;
     ZkBlock *blocks = (ZkBlock *)c.blocks.p;
-    uint64_t *words = (uint64_t *)c.words.p, *d_offs = (uint64_t *)s.d_off.p;
-    const uint8_t *comp = (const uint8_t *)s.d_in.p;
+    uint64_t *words = (uint64_t *)c.words.p, *d_offs = (uint64_t *)s.meta.p;
+    const uint8_t *comp = (const uint8_t *)s.in.p;
     const uint32_t gen = ++hp->small_gen;
-    zk_launch_small_walk(st, h_comp, csz, h_offs, count, dsz, block_cap, seq_cap, (uint8_t *)s.d_in.p, d_offs, infos, (ZkFrameBase *)c.bases.p, blocks, words);
+    zk_launch_small_walk(st, h_comp, csz, h_offs, count, dsz, block_cap, seq_cap, (uint8_t *)s.in.p, d_offs, infos, (ZkFrameBase *)c.bases.p, blocks, words);
     uint32_t groups = (block_cap + 15) / 16;
     if (groups > 32) groups = 32;
     zk_launch_small_entropy(st, comp, blocks, words, (uint8_t *)c.lit.p, (ZkSeqP *)c.seqs.p, groups, e->choice.small_path == 2);
@@ -466,9 +496,9 @@ static int zk_decode_small(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src
     const ZkSegPlan sp = zk_seg_plan_small(shape);
     ZkSegScratch sgs{};
     if (sp.on && (rc = zk_dec_seg_scratch(e, c, count, sp, dsz, block_cap, sgs))) return rc;
-    const zk_dec_args a{comp, csz, d_offs, d_offs + count + 1, 0, count, nullptr, nullptr, s.d_out.p, dsz, verify, s.d_st.p, d_prefix, d_prefix ? prefix_len : 0};
+    const zk_dec_args a{comp, csz, d_offs, d_offs + count + 1, 0, count, nullptr, nullptr, s.out.p, dsz, verify, s.st.p, d_prefix, d_prefix ? prefix_len : 0};
     if ((rc = zk_dec_exec_checksums(e, c, st, a, sp.on ? &sgs : nullptr, e->choice, false, prog, nullptr))) return rc;
-    zk_launch_small_publish(st, infos, d_offs, count, (const uint8_t *)s.d_out.p, dsz ? h_out : nullptr, (int32_t *)s.d_st.p, h_status, words, hp->pin_flag, gen);
+    zk_launch_small_publish(st, infos, d_offs, count, (const uint8_t *)s.out.p, dsz ? h_out : nullptr, (int32_t *)s.st.p, h_status, words, hp->pin_flag, gen);
     // completion: the last workgroup of the publish kernel writes the generation into pinned memory
     volatile uint32_t *flag = hp->pin_flag;
     const auto t0 = std::chrono::steady_clock::now();
@@ -482,11 +512,7 @@ static int zk_decode_small(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src
     std::atomic_thread_fence(std::memory_order_acquire);
     if (h_status[0] == (int32_t)0xFFFFFFFF) { *fallback = true; return 0; }
     if (!dst_pinned && dsz) memcpy(dst, h_out, (size_t)dsz);
-    uint32_t ok = count;
-    for (uint32_t i = 0; i < count; i++) if (h_status[i] != 0) { ok = i; break; }
-    if (frame_status) memcpy(frame_status, h_status, (size_t)count * 4);
-    if (n_ok) *n_ok = ok;
-    return ok == count ? 0 : -(int)h_status[ok];
+    return zk_frames_verdict(h_status, count, frame_status, n_ok);
 }
 
 int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, const uint64_t *d_off, uint32_t first, uint32_t count,
@@ -540,10 +566,10 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
     // ---- pinned meta: rebased offsets of every chunk + the status words of every frame (every allocation that can fail comes
     // before the registration windows start: their pool tasks point at this frame's objects)
     const size_t off_bytes = ((size_t)(count + nchunks) * 16 + 63) & ~(size_t)63;
-    if ((rc = zk_pin_grow(e, hp->pin_meta, hp->pin_meta_cap, off_bytes + (size_t)count * 4 + 64))) return rc;
+    if ((rc = zk_pin_reserve(e, hp->pin_meta, hp->pin_meta_cap, off_bytes + (size_t)count * 4 + 64))) return rc;
     uint64_t *pin_offs = (uint64_t *)hp->pin_meta;
     int32_t *pin_status = (int32_t *)(hp->pin_meta + off_bytes);
-    if (small) { if ((rc = zk_pin_grow(e, hp->pin_small, hp->pin_small_cap, (size_t)max_c + (size_t)total_d + 256))) return rc; }
+    if (small) { if ((rc = zk_pin_reserve(e, hp->pin_small, hp->pin_small_cap, (size_t)max_c + (size_t)total_d + 256))) return rc; }
     // caller memory that is not pinned already is pinned on the fly, unit by unit, ahead of the copies (ZkRegWindow)
     ZkRegWindow wsrc, wdst;
     if (!small && src.mem && !src_pinned) wsrc.start(hp->pool, src.mem + c_lo, (size_t)(c_off[first + count] - c_lo));
@@ -563,41 +589,18 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
         const uint32_t nf = ck.f1 - ck.f0;
         const uint64_t csz = ck.c1 - ck.c0;
         int r;
-        if ((r = zk_devbuf_reserve(e, s.d_in, (size_t)csz + 64))) return r;
-        if ((r = zk_devbuf_reserve(e, s.d_out, (size_t)(ck.d1 - ck.d0) + 64))) return r;
-        if ((r = zk_devbuf_reserve(e, s.d_off, (size_t)(nf + 1) * 16))) return r;
-        if ((r = zk_devbuf_reserve(e, s.d_st, (size_t)nf * 4 + 16))) return r;
+        if ((r = zk_devbuf_reserve(e, s.in, (size_t)csz + 64))) return r;
+        if ((r = zk_devbuf_reserve(e, s.out, (size_t)(ck.d1 - ck.d0) + 64))) return r;
+        if ((r = zk_devbuf_reserve(e, s.meta, (size_t)(nf + 1) * 16))) return r;
+        if ((r = zk_devbuf_reserve(e, s.st, (size_t)nf * 4 + 16))) return r;
         // the chunk's HBM buffers were last used by chunk i - nslots: its D2H must have run
         if (s.out_pending) ZK_HIP(hipStreamWaitEvent(hp->s_h2d, s.ev_out, 0));
         uint64_t *o = pin_offs + offs_at;
         offs_at += (size_t)(nf + 1) * 2;
         for (uint32_t k = 0; k <= nf; k++) { o[k] = c_off[first + ck.f0 + k] - ck.c0; o[nf + 1 + k] = d_off[first + ck.f0 + k] - ck.d0; }
-        ZK_HIP(hipMemcpyAsync(s.d_off.p, o, (size_t)(nf + 1) * 16, hipMemcpyHostToDevice, hp->s_h2d));
-        if (src_pinned) {
-            if (csz) ZK_HIP(hipMemcpyAsync(s.d_in.p, src.mem + ck.c0, csz, hipMemcpyHostToDevice, hp->s_h2d));
-        } else if (small) {
-            if ((r = zk_src_fill(e, hp, src, ck.c0, hp->pin_small, (size_t)csz))) return r;
-            if (csz) ZK_HIP(hipMemcpyAsync(s.d_in.p, hp->pin_small, csz, hipMemcpyHostToDevice, hp->s_h2d));
-        } else {
-            for (uint64_t at = 0; at < csz;) {
-                if (src.mem && wsrc.ok(src.mem + ck.c0 + at)) {             // straight from the caller's (now pinned) pages
-                    const size_t sp = wsrc.span(src.mem + ck.c0 + at), n = (size_t)(csz - at < sp ? csz - at : sp);
-                    ZK_HIP(hipMemcpyAsync((uint8_t *)s.d_in.p + at, src.mem + ck.c0 + at, n, hipMemcpyHostToDevice, hp->s_h2d));
-                    at += n;
-                    continue;
-                }
-                if ((r = zk_hostpipe_rings(e, hp))) return r;
-                const size_t n = (size_t)(csz - at < zk_hostpipe::PIECE ? csz - at : zk_hostpipe::PIECE);
-                const int k = hp->ring_in.acquire();
-                ZkRing::Piece &pc = hp->ring_in.pc[k];
-                if ((r = zk_src_fill(e, hp, src, ck.c0 + at, pc.p, n))) return r;
-                ZK_HIP(hipMemcpyAsync((uint8_t *)s.d_in.p + at, pc.p, n, hipMemcpyHostToDevice, hp->s_h2d));
-                ZK_HIP(hipEventRecord(pc.ev, hp->s_h2d));
-                pc.ev_pending = true;
-                at += n;
-            }
-        }
-        ZK_HIP(hipMemsetAsync((uint8_t *)s.d_in.p + csz, 0, 16, hp->s_h2d));     // the readers may touch ZK_COMP_PADDING bytes past the end
+        ZK_HIP(hipMemcpyAsync(s.meta.p, o, (size_t)(nf + 1) * 16, hipMemcpyHostToDevice, hp->s_h2d));
+        if ((r = zk_pipe_upload(e, hp, src, ck.c0, (uint8_t *)s.in.p, csz, src_pinned, small, wsrc))) return r;
+        ZK_HIP(hipMemsetAsync((uint8_t *)s.in.p + csz, 0, 16, hp->s_h2d));     // the readers may touch ZK_COMP_PADDING bytes past the end
         ZK_HIP(hipEventRecord(s.ev_in, hp->s_h2d));
         return 0;
     };
@@ -610,36 +613,33 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
         zk_engine::DecCtx &c = e->dctx[i % nctx];
         ZK_HIP(hipStreamWaitEvent(c.st, s.ev_in, 0));
         if (s.out_pending) ZK_HIP(hipStreamWaitEvent(c.st, s.ev_out, 0));
-        const uint64_t *dc = (const uint64_t *)s.d_off.p, *dd = dc + nf + 1;
-        zk_dec_args a{s.d_in.p, ck.c1 - ck.c0, dc, dd, 0, nf, nullptr, nullptr, s.d_out.p, dsz, verify, s.d_st.p, d_prefix, d_prefix ? prefix_len : 0};
+        const uint64_t *dc = (const uint64_t *)s.meta.p, *dd = dc + nf + 1;
+        zk_dec_args a{s.in.p, ck.c1 - ck.c0, dc, dd, 0, nf, nullptr, nullptr, s.out.p, dsz, verify, s.st.p, d_prefix, d_prefix ? prefix_len : 0};
         a.single_queue = nchunks > 1;                       // whole chunks overlap instead of huf || fse
         a.mark_exec = true;                                 // the bytes travel back while the checksum chains still run; the status words follow them
         zk_profiling_off quiet(e, nchunks > 1);             // per-kernel events describe one synchronous batch
         int r = zk_decode_enqueue(e, c, c.st, a);
         if (r) return r;
-        ZK_HIP(hipEventRecord(s.ev_dec, c.st));
+        ZK_HIP(hipEventRecord(s.ev_run, c.st));
         ZK_HIP(hipStreamWaitEvent(hp->s_d2h, c.ev_exec, 0));
         uint8_t *out = dst + (ck.d0 - d_lo);
         if (dst_pinned) {
-            if (dsz) ZK_HIP(hipMemcpyAsync(out, s.d_out.p, dsz, hipMemcpyDeviceToHost, hp->s_d2h));
+            if (dsz) ZK_HIP(hipMemcpyAsync(out, s.out.p, dsz, hipMemcpyDeviceToHost, hp->s_d2h));
         } else if (small) {
             uint8_t *stage = hp->pin_small + ((max_c + 63) & ~(uint64_t)63);
-            if (dsz) ZK_HIP(hipMemcpyAsync(stage, s.d_out.p, dsz, hipMemcpyDeviceToHost, hp->s_d2h));
+            if (dsz) ZK_HIP(hipMemcpyAsync(stage, s.out.p, dsz, hipMemcpyDeviceToHost, hp->s_d2h));
         } else {
             for (uint64_t at = 0; at < dsz;) {
                 if (wdst.ok(out + at)) {                                     // straight into the caller's (now pinned) pages
                     const size_t sp = wdst.span(out + at), n = (size_t)(dsz - at < sp ? dsz - at : sp);
-                    ZK_HIP(hipMemcpyAsync(out + at, (const uint8_t *)s.d_out.p + at, n, hipMemcpyDeviceToHost, hp->s_d2h));
+                    ZK_HIP(hipMemcpyAsync(out + at, (const uint8_t *)s.out.p + at, n, hipMemcpyDeviceToHost, hp->s_d2h));
                     at += n;
                     continue;
                 }
                 if ((r = zk_hostpipe_rings(e, hp))) return r;
                 const size_t n = (size_t)(dsz - at < zk_hostpipe::PIECE ? dsz - at : zk_hostpipe::PIECE);
-                const int k = hp->ring_out.acquire();
-                ZkRing::Piece &pc = hp->ring_out.pc[k];
-                ZK_HIP(hipMemcpyAsync(pc.p, (const uint8_t *)s.d_out.p + at, n, hipMemcpyDeviceToHost, hp->s_d2h));
-                ZK_HIP(hipEventRecord(pc.ev, hp->s_d2h));
-                hp->ring_out.hold(k);
+                const int k = zk_pipe_download_piece(e, hp, (const uint8_t *)s.out.p + at, n);
+                if (k < 0) return k;
                 uint8_t *to = out + at;
                 ZkRing *ring = &hp->ring_out;
                 ZkPool *pool = hp->pool;
@@ -661,8 +661,8 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
                 at += n;
             }
         }
-        ZK_HIP(hipStreamWaitEvent(hp->s_d2h, s.ev_dec, 0));
-        ZK_HIP(hipMemcpyAsync(pin_status + ck.f0, s.d_st.p, (size_t)nf * 4, hipMemcpyDeviceToHost, hp->s_d2h));
+        ZK_HIP(hipStreamWaitEvent(hp->s_d2h, s.ev_run, 0));
+        ZK_HIP(hipMemcpyAsync(pin_status + ck.f0, s.st.p, (size_t)nf * 4, hipMemcpyDeviceToHost, hp->s_d2h));
         ZK_HIP(hipEventRecord(s.ev_out, hp->s_d2h));
         s.out_pending = true;
         return 0;
@@ -688,11 +688,7 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
     ZK_HIP(hipGetLastError());
     if (nchunks == 1) zk_profile_collect(e);
     if (small && !dst_pinned && total_d) memcpy(dst, hp->pin_small + ((max_c + 63) & ~(uint64_t)63), (size_t)total_d);
-    uint32_t ok = count;
-    for (uint32_t i = 0; i < count; i++) if (pin_status[i] != 0) { ok = i; break; }
-    if (frame_status) memcpy(frame_status, pin_status, (size_t)count * 4);
-    if (n_ok) *n_ok = ok;
-    return ok == count ? 0 : -(int)pin_status[ok];
+    return zk_frames_verdict(pin_status, count, frame_status, n_ok);
 }
 
 extern "C" int zk_decode_frames(zk_engine *e, const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off,
@@ -746,11 +742,13 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
     if (!small) { if ((rc = zk_hostpipe_rings(e, hp))) return rc; }                 // the compressed bytes travel back through the ring
     const uint64_t max_in = per * frame_size < n ? per * frame_size : n;
     const uint64_t max_bound = zk_compress_bound(max_in, frame_size);
-    if (small) { if ((rc = zk_pin_grow(e, hp->pin_small, hp->pin_small_cap, (size_t)max_in + (size_t)max_bound + 256))) return rc; }
-    if ((rc = zk_pin_grow(e, hp->pin_meta, hp->pin_meta_cap, (size_t)per * 8 * 2 + 64))) return rc;     // (c, d) sizes of two chunks
+    if (small) { if ((rc = zk_pin_reserve(e, hp->pin_small, hp->pin_small_cap, (size_t)max_in + (size_t)max_bound + 256))) return rc; }
+    if ((rc = zk_pin_reserve(e, hp->pin_meta, hp->pin_meta_cap, (size_t)per * 8 * 2 + 64))) return rc;     // (c, d) sizes of two chunks
     ZkRegWindow wsrc;                                       // (after every allocation that can fail: its pool tasks point at this frame)
     if (!small && !src_pinned) wsrc.start(hp->pool, src, (size_t)n);
     hipStream_t st = e->stream;
+    zk_host_src hsrc;
+    hsrc.mem = src;
 
     auto chunk_range = [&](size_t i, uint64_t &f0, uint64_t &nf, uint64_t &b0, uint64_t &bn) {
         f0 = (uint64_t)i * per; nf = nf64 - f0 < per ? nf64 - f0 : per;
@@ -758,53 +756,36 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
     };
     auto prep = [&](size_t i) -> int {
         uint64_t f0, nf, b0, bn; chunk_range(i, f0, nf, b0, bn);
-        zk_hostpipe::ESlot &s = hp->es[i & 1];
+        zk_hostpipe::Slot &s = hp->es[i & 1];
         int r;
-        if ((r = zk_devbuf_reserve(e, s.d_src, (size_t)bn + 64))) return r;      // (d_dst / d_sizes of the slot may still be on their way down: enqueue() sizes them)
-        if (src_pinned) { if (bn) ZK_HIP(hipMemcpyAsync(s.d_src.p, src + b0, bn, hipMemcpyHostToDevice, hp->s_h2d)); }
-        else if (small) { memcpy(hp->pin_small, src + b0, (size_t)bn); if (bn) ZK_HIP(hipMemcpyAsync(s.d_src.p, hp->pin_small, bn, hipMemcpyHostToDevice, hp->s_h2d)); }
-        else for (uint64_t at = 0; at < bn;) {
-            if (wsrc.ok(src + b0 + at)) {                                   // straight from the caller's (now pinned) pages
-                const size_t sp = wsrc.span(src + b0 + at), len = (size_t)(bn - at < sp ? bn - at : sp);
-                ZK_HIP(hipMemcpyAsync((uint8_t *)s.d_src.p + at, src + b0 + at, len, hipMemcpyHostToDevice, hp->s_h2d));
-                at += len;
-                continue;
-            }
-            const size_t len = (size_t)(bn - at < zk_hostpipe::PIECE ? bn - at : zk_hostpipe::PIECE);
-            const int k = hp->ring_in.acquire();
-            ZkRing::Piece &pc = hp->ring_in.pc[k];
-            hp->pool->copy(pc.p, src + b0 + at, len);
-            ZK_HIP(hipMemcpyAsync((uint8_t *)s.d_src.p + at, pc.p, len, hipMemcpyHostToDevice, hp->s_h2d));
-            ZK_HIP(hipEventRecord(pc.ev, hp->s_h2d));
-            pc.ev_pending = true;
-            at += len;
-        }
+        if ((r = zk_devbuf_reserve(e, s.in, (size_t)bn + 64))) return r;      // (out / meta of the slot may still be on their way down: enqueue() sizes them)
+        if ((r = zk_pipe_upload(e, hp, hsrc, b0, (uint8_t *)s.in.p, bn, src_pinned, small, wsrc))) return r;
         ZK_HIP(hipEventRecord(s.ev_in, hp->s_h2d));
         return 0;
     };
     auto enqueue = [&](size_t i) -> int {
         uint64_t f0, nf, b0, bn; chunk_range(i, f0, nf, b0, bn);
-        zk_hostpipe::ESlot &s = hp->es[i & 1];
+        zk_hostpipe::Slot &s = hp->es[i & 1];
         int r0;
-        if ((r0 = zk_devbuf_reserve(e, s.d_dst, (size_t)zk_compress_bound(bn, frame_size) + 64))) return r0;      // the chunk two back has been handed to the sink by now
-        if ((r0 = zk_devbuf_reserve(e, s.d_sizes, (size_t)nf * 8 + 64))) return r0;
+        if ((r0 = zk_devbuf_reserve(e, s.out, (size_t)zk_compress_bound(bn, frame_size) + 64))) return r0;      // the chunk two back has been handed to the sink by now
+        if ((r0 = zk_devbuf_reserve(e, s.meta, (size_t)nf * 8 + 64))) return r0;
         ZK_HIP(hipStreamWaitEvent(st, s.ev_in, 0));
-        if (s.out_pending) ZK_HIP(hipStreamWaitEvent(st, s.ev_out, 0));       // the chunk two back has left d_dst
-        uint32_t *dc = (uint32_t *)s.d_sizes.p, *dd = dc + nf;
-        zk_enc_args a{s.d_src.p, bn, frame_size, level, checksum, d_prefix, d_prefix ? prefix_len : 0, s.d_dst.p,
+        if (s.out_pending) ZK_HIP(hipStreamWaitEvent(st, s.ev_out, 0));       // the chunk two back has left `out`
+        uint32_t *dc = (uint32_t *)s.meta.p, *dd = dc + nf;
+        zk_enc_args a{s.in.p, bn, frame_size, level, checksum, d_prefix, d_prefix ? prefix_len : 0, s.out.p,
                       zk_compress_bound(bn, frame_size), dc, dd};
         uint32_t nfo = 0;
         zk_profiling_off quiet(e, nchunks > 1);
         int r = zk_encode_enqueue(e, a, st, &nfo);
         if (r) return r;
-        ZK_HIP(hipEventRecord(s.ev_enc, st));
+        ZK_HIP(hipEventRecord(s.ev_run, st));
         return 0;
     };
     // wait for chunk i, bring its bytes and seek entries back and hand them to the sink (in order, on this thread)
     auto finish = [&](size_t i, bool more) -> int {
         uint64_t f0, nf, b0, bn; chunk_range(i, f0, nf, b0, bn);
-        zk_hostpipe::ESlot &s = hp->es[i & 1];
-        ZK_HIP(hipEventSynchronize(s.ev_enc));
+        zk_hostpipe::Slot &s = hp->es[i & 1];
+        ZK_HIP(hipEventSynchronize(s.ev_run));
         const uint64_t total = e->h_words[ZK_HW_ENC_TOTAL];
         if (nchunks == 1) zk_profile_collect(e);
         int r = 0;
@@ -813,10 +794,10 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
         // (issued behind this chunk's download and sink, its upload used to arrive after the GPU had run dry)
         if (i + 2 < nchunks && (r = prep(i + 2))) return r;
         uint32_t *sizes = (uint32_t *)hp->pin_meta + (i & 1) * (size_t)per * 2;
-        ZK_HIP(hipMemcpyAsync(sizes, s.d_sizes.p, (size_t)nf * 8, hipMemcpyDeviceToHost, hp->s_d2h));
+        ZK_HIP(hipMemcpyAsync(sizes, s.meta.p, (size_t)nf * 8, hipMemcpyDeviceToHost, hp->s_d2h));
         if (small) {
             uint8_t *stage = hp->pin_small + ((max_in + 63) & ~(uint64_t)63);
-            ZK_HIP(hipMemcpyAsync(stage, s.d_dst.p, total, hipMemcpyDeviceToHost, hp->s_d2h));
+            ZK_HIP(hipMemcpyAsync(stage, s.out.p, total, hipMemcpyDeviceToHost, hp->s_d2h));
             ZK_HIP(hipStreamSynchronize(hp->s_d2h));
             return sink(user, stage, total, sizes, sizes + nf, (uint32_t)nf) ? ZK_ERR_IO : 0;
         }
@@ -826,11 +807,8 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
         while (at < total || !inflight.empty()) {
             while (at < total && inflight.size() < 4) {
                 const size_t len = (size_t)(total - at < zk_hostpipe::PIECE ? total - at : zk_hostpipe::PIECE);
-                const int k = hp->ring_out.acquire();
-                ZkRing::Piece &pc = hp->ring_out.pc[k];
-                ZK_HIP(hipMemcpyAsync(pc.p, (const uint8_t *)s.d_dst.p + at, len, hipMemcpyDeviceToHost, hp->s_d2h));
-                ZK_HIP(hipEventRecord(pc.ev, hp->s_d2h));
-                hp->ring_out.hold(k);
+                const int k = zk_pipe_download_piece(e, hp, (const uint8_t *)s.out.p + at, len);
+                if (k < 0) return k;
                 inflight.push_back({k, len});
                 at += len;
                 if (at >= total) { ZK_HIP(hipEventRecord(s.ev_out, hp->s_d2h)); s.out_pending = true; }

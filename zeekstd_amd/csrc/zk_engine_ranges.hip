@@ -11,15 +11,6 @@
 #include "zk_kernels.h"
 #include "zk_ranges.h"
 
-#define ZK_HIP(call)                                                                                 \
-    do {                                                                                             \
-        hipError_t _e = (call);                                                                      \
-        if (_e != hipSuccess) {                                                                      \
-            e->last_err = std::string(#call) + ": " + hipGetErrorString(_e);                         \
-            return ZK_ERR_HIP;                                                                       \
-        }                                                                                            \
-    } while (0)
-
 extern "C" uint64_t zk_engine_ranges_frames_decoded(const zk_engine *e) { return e ? e->ranges_frames : 0; }
 
 namespace {
