@@ -44,6 +44,10 @@ def lib():
         l.zko_frame_decode_prefix.restype = C.c_int64
         l.zko_frame_decode_prefix.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_size_t), C.c_int, C.POINTER(FrameStats), C.c_char_p, C.c_size_t]
+        l.zko_frame_decode_dict.restype = C.c_int64
+        l.zko_frame_decode_dict.argtypes = l.zko_frame_decode_prefix.argtypes
+        l.zko_dict_check.restype = C.c_int64
+        l.zko_dict_check.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
         l.zko_gen_text.restype = None
         l.zko_gen_text.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64]
         l.zko_gen_chunks.restype = None
@@ -133,14 +137,31 @@ class OracleError(Exception):
         self.code = code
 
 
-def frame_decode(src: bytes, dst_cap: int, verify: bool = True, want_stats: bool = False, prefix: bytes = None):
+def dict_check(dictionary: bytes):
+    """-> (Dictionary_ID, offset of the content) of a dictionary the oracle loads (0, 0: raw content); OracleError(30) for one that
+    ZSTD_loadDEntropy refuses"""
+    dictionary = bytes(dictionary)
+    i, off = C.c_uint32(), C.c_size_t()
+    r = lib().zko_dict_check(dictionary, len(dictionary), C.byref(i), C.byref(off))
+    if r < 0:
+        raise OracleError(-r)
+    return i.value, off.value
+
+
+def frame_decode(src: bytes, dst_cap: int, verify: bool = True, want_stats: bool = False, prefix: bytes = None, dictionary: bytes = None):
     """Decode ONE frame at the start of src. Returns (decoded bytes, consumed[, stats]).
-    prefix: raw-content prefix referenced for the frame (ZSTD_DCtx_refPrefix semantics)."""
+    prefix: raw-content prefix referenced for the frame (ZSTD_DCtx_refPrefix semantics).
+    dictionary: a zstd dictionary loaded for the frame (ZSTD_decompress_usingDict semantics): a formatted one lends its ID, tree, tables,
+    repeat offsets and content; anything else is raw content."""
     src = bytes(src)
     out = C.create_string_buffer(max(dst_cap, 1))
     used = C.c_size_t()
     st = FrameStats()
-    if prefix:
+    assert not (prefix and dictionary)
+    if dictionary:
+        dictionary = bytes(dictionary)
+        r = lib().zko_frame_decode_dict(src, len(src), out, dst_cap, C.byref(used), int(verify), C.byref(st), dictionary, len(dictionary))
+    elif prefix:
         prefix = bytes(prefix)
         r = lib().zko_frame_decode_prefix(src, len(src), out, dst_cap, C.byref(used), int(verify), C.byref(st), prefix, len(prefix))
     else:

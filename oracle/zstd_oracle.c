@@ -27,6 +27,8 @@
  *   zko_xxh64            XXH64 (content checksum, encode.rs:163-167 enables it)
  *   zko_frame_decode     full-format zstd frame decoder (what ZSTD_decompressStream does
  *                        for decode.rs:242-256)
+ *   zko_frame_decode_dict  the same against a dictionary (RFC 8878 section 5; what ZSTD_decompress_usingDict does):
+ *                        a formatted one lends its ID, tree, tables, repeat offsets and content, anything else its bytes
  *   zko_frame_encode     a small valid zstd frame encoder (greedy single-hash LZ +
  *                        Huffman literals + FSE sequences; what ZSTD_compressStream2
  *                        does for encode.rs:340-346/442-464 -- payload bytes are
@@ -53,6 +55,7 @@ enum {
     ZKO_E_WINDOW_TOO_LARGE = 16,
     ZKO_E_CORRUPTION = 20,
     ZKO_E_CHECKSUM_WRONG = 22,
+    ZKO_E_DICT_CORRUPTED = 30,
     ZKO_E_DICT_WRONG = 32,
     ZKO_E_DST_TOO_SMALL = 70,
     ZKO_E_SRC_SIZE_WRONG = 72,
@@ -484,9 +487,86 @@ i64 zko_frame_decode(const u8 *src, size_t src_size, u8 *dst, size_t dst_cap, si
     return zko_frame_decode_prefix(src, src_size, dst, dst_cap, consumed, verify, fs, NULL, 0);
 }
 
+static i64 frame_decode_impl(const u8 *src, size_t src_size, u8 *dst, size_t dst_cap, size_t *consumed,
+                             int verify, zko_frame_stats *fs, const u8 *prefix, size_t plen, const dstate *init, u32 dict_id);
+
 /* the same with a raw-content prefix referenced for this frame (ZSTD_DCtx_refPrefix semantics) */
 i64 zko_frame_decode_prefix(const u8 *src, size_t src_size, u8 *dst, size_t dst_cap, size_t *consumed,
                             int verify, zko_frame_stats *fs, const u8 *prefix, size_t plen)
+{
+    return frame_decode_impl(src, src_size, dst, dst_cap, consumed, verify, fs, prefix, plen, NULL, 0);
+}
+
+/* A formatted dictionary (RFC 8878 5): magic | Dictionary_ID | Huffman tree description | FSE descriptions of the Offset, Match_Length
+ * and Literals_Length codes | three repeat offsets | content, read with the readers above into the state a frame starts from.
+ * Returns the content's offset, 0 for a raw-content dictionary (fewer than 8 bytes, or another magic: every byte is content), or
+ * -30 for what ZSTD_loadDEntropy refuses: a description that does not parse or build, an accuracy log or a symbol above the table's
+ * limit, a repeat offset that is 0 or larger than the content. */
+static i64 dict_load(const u8 *dict, size_t dlen, dstate *st, u32 *id)
+{
+    *id = 0;
+    if (!dict || dlen < 8 || rd32(dict) != 0xEC30A437u) return 0;
+    *id = rd32(dict + 4);
+    size_t p = 8;
+    i64 r = huf_read_table(&st->huf, dict + p, dlen - p);
+    if (r < 0) return ERR(ZKO_E_DICT_CORRUPTED);
+    p += (size_t)r;
+    /* HUF_readStats: the symbols of weight 1 (one cell each, the longest codes) are two at least and even in number; a frame's tree
+     * is not held to that here, a dictionary's is -- libzstd does not load one that fails it */
+    u32 ones = 0;
+    for (u32 i = 0; i < (1u << st->huf.maxbits); i++) ones += st->huf.cell[i].nb == st->huf.maxbits;
+    if (ones < 2 || (ones & 1)) return ERR(ZKO_E_DICT_CORRUPTED);
+    static const int max_sym[3] = {31, 52, 35}, max_al[3] = {8, 9, 9};
+    fse_table *tab[3] = {&st->of, &st->ml, &st->ll};
+    for (int k = 0; k < 3; k++) {
+        short norm[64]; int nsym, al;
+        r = fse_read_ncount(dict + p, dlen - p, max_sym[k], max_al[k], norm, &nsym, &al);
+        if (r < 0 || fse_build(tab[k], norm, nsym, al)) return ERR(ZKO_E_DICT_CORRUPTED);
+        p += (size_t)r;
+    }
+    st->ll_valid = st->of_valid = st->ml_valid = 1;
+    if (dlen - p < 12) return ERR(ZKO_E_DICT_CORRUPTED);
+    const size_t content = dlen - p - 12;
+    for (int i = 0; i < 3; i++) {
+        st->rep[i] = rd32(dict + p + 4 * i);
+        if (st->rep[i] == 0 || st->rep[i] > content) return ERR(ZKO_E_DICT_CORRUPTED);
+    }
+    return (i64)(p + 12);
+}
+
+/* 0 when the dictionary loads (formatted or raw content), -30 otherwise; *id and *content_off as ZDICT_getDictID / ZDICT_getDictHeaderSize */
+i64 zko_dict_check(const u8 *dict, size_t dlen, u32 *id, size_t *content_off)
+{
+    dstate *st = (dstate *)calloc(1, sizeof *st);
+    if (!st) return ERR(ZKO_E_GENERIC);
+    u32 i = 0;
+    const i64 r = dict_load(dict, dlen, st, &i);
+    free(st);
+    if (r < 0) return r;
+    if (id) *id = i;
+    if (content_off) *content_off = (size_t)r;
+    return 0;
+}
+
+/* ONE frame against a dictionary (ZSTD_decompress_usingDict semantics): a frame may name the dictionary's ID, 0 or carry no field */
+i64 zko_frame_decode_dict(const u8 *src, size_t src_size, u8 *dst, size_t dst_cap, size_t *consumed,
+                          int verify, zko_frame_stats *fs, const u8 *dict, size_t dlen)
+{
+    if (!dict) dlen = 0;
+    dstate *init = (dstate *)calloc(1, sizeof *init);
+    if (!init) return ERR(ZKO_E_GENERIC);
+    u32 id = 0;
+    i64 r = dict_load(dict, dlen, init, &id);
+    if (r >= 0)
+        r = r == 0 ? frame_decode_impl(src, src_size, dst, dst_cap, consumed, verify, fs, dict, dlen, NULL, 0)
+                   : frame_decode_impl(src, src_size, dst, dst_cap, consumed, verify, fs, dict + r, dlen - (size_t)r, init, id);
+    free(init);
+    return r;
+}
+
+/* init: the state a frame starts from (a formatted dictionary's tree, tables and repeat offsets; NULL: none, 1 / 4 / 8), dict_id: its ID */
+static i64 frame_decode_impl(const u8 *src, size_t src_size, u8 *dst, size_t dst_cap, size_t *consumed,
+                             int verify, zko_frame_stats *fs, const u8 *prefix, size_t plen, const dstate *init, u32 dict_id)
 {
     if (!prefix) plen = 0;
     if (fs) memset(fs, 0, sizeof *fs);
@@ -516,7 +596,7 @@ i64 zko_frame_decode_prefix(const u8 *src, size_t src_size, u8 *dst, size_t dst_
     int dl = did_len[did], fl = fcs_len[fcs_flag];
     if (fcs_flag == 0 && single) fl = 1;
     if (p + (size_t)dl + (size_t)fl > src_size) return ERR(ZKO_E_SRC_SIZE_WRONG);
-    if (dl) { u32 id = 0; for (int i = 0; i < dl; i++) id |= (u32)src[p + i] << (8 * i); if (id) return ERR(ZKO_E_DICT_WRONG); }
+    if (dl) { u32 id = 0; for (int i = 0; i < dl; i++) id |= (u32)src[p + i] << (8 * i); if (id && id != dict_id) return ERR(ZKO_E_DICT_WRONG); }
     p += (size_t)dl;
     u64 fcs = 0;
     if (fl == 1) fcs = src[p]; else if (fl == 2) fcs = (u64)rd16(src + p) + 256; else if (fl == 4) fcs = rd32(src + p); else if (fl == 8) fcs = rd64(src + p);
@@ -527,9 +607,12 @@ i64 zko_frame_decode_prefix(const u8 *src, size_t src_size, u8 *dst, size_t dst_
 
     dstate *st = (dstate *)malloc(sizeof *st);
     if (!st) return ERR(ZKO_E_GENERIC);
+    if (init) *st = *init;
+    else {
+        st->huf.valid = 0; st->ll_valid = st->of_valid = st->ml_valid = 0;
+        st->rep[0] = 1; st->rep[1] = 4; st->rep[2] = 8;
+    }
     st->lit = (u8 *)malloc(131072 + 32);
-    st->huf.valid = 0; st->ll_valid = st->of_valid = st->ml_valid = 0;
-    st->rep[0] = 1; st->rep[1] = 4; st->rep[2] = 8;
     size_t out = 0;
     i64 rc = 0;
     for (;;) {

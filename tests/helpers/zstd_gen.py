@@ -22,7 +22,18 @@ Keywords beyond the defaults (with the defaults a seed gives the bytes it always
   shared_tables    frames of 16 ... 80 blocks whose first block with sequences describes all three tables over every code the frame may use;
                    later blocks mostly say Repeat_Mode (or Predefined_Mode) for all three, seldom redefine one table, use RLE_Mode or mix
   max_ll / max_ml  upper ends of a long tail of literal lengths / match lengths (drawn by code, so the codes with 11 ... 16 extra bits come up),
-                   up to the block size; long matches mostly at offset 1.  max_lit has to allow the literals"""
+                   up to the block size; long matches mostly at offset 1.  max_lit has to allow the literals
+  dictionary       a Dictionary (the model make_dictionary / raw_dictionary return): the frame is written against it -- its content lies below
+                   the frame's first byte, and with a formatted one the frame starts from its repeat offsets, its Huffman tree (Treeless
+                   literals in a first block) and its three tables (Repeat_Mode per table, independently, until a block says otherwise);
+                   the Dictionary_ID field has any width that holds the ID, or is absent.  Offsets stay within the window and within what
+                   is available, as with a prefix.  Features (they count for blocks the frame keeps): dict_treeless_first_1stream /
+                   _4streams (the frame's first compressed block), dict_ll_repeat / dict_of_repeat / dict_ml_repeat and, with the mode of
+                   each other table, dict_ll_repeat_of_mode0 ..., dict_table_after_redefine (another table was described or set by an
+                   earlier block), dict_first_comp_not_block0 (the first compressed block uses the dictionary and is not the frame's
+                   first block), dict_rep_first_idx0 ... 3 (the frame's first sequence takes a repeat offset of the dictionary; 3 is
+                   Repeated_Offset1 - 1), off_into_dict, off_dict_first_byte, match_straddles_frame_start, did_width1 / 2 / 4, did_absent.
+                   stats=True: huf_def is "dict" where the tree in use is the dictionary's"""
 import random
 import struct
 
@@ -172,10 +183,12 @@ class HufCode:
                     pos += 1 << (wt - 1)
         assert pos == 1 << self.maxbits
 
-    def description(self, rng):
-        """-> (bytes, "direct" | "fse") or None: four bits per weight, or the weights as an FSE stream on two interleaved states (RFC 8878 4.2.1.2)"""
+    def description(self, rng, form=None):
+        """-> (bytes, "direct" | "fse") or None: four bits per weight, or the weights as an FSE stream on two interleaved states (RFC 8878 4.2.1.2).
+        form: the one to take (None where the weights do not allow it); drawn without"""
         w = self.weights[:-1]
-        if len(w) <= 128 and (len(w) < 2 or rng.random() < 0.5):
+        if form == "direct" and len(w) > 128 or form == "fse" and len(w) < 2: return None
+        if form == "direct" or (form is None and len(w) <= 128 and (len(w) < 2 or rng.random() < 0.5)):
             out = bytearray([127 + len(w)])
             for i in range(0, len(w), 2):
                 out.append((w[i] << 4) | (w[i + 1] if i + 1 < len(w) else 0))
@@ -215,10 +228,15 @@ class HufCode:
 
 
 class FrameGen:
-    def __init__(self, seed, max_blocks=6, max_seq=300, max_lit=3000, prefix=b"", dense=False, shared_tables=False, max_ll=None, max_ml=None):
+    def __init__(self, seed, max_blocks=6, max_seq=300, max_lit=3000, prefix=b"", dense=False, shared_tables=False, max_ll=None, max_ml=None, dictionary=None):
         self.rng = random.Random(seed)
         self.want_dense = dense                              # one block of the frame with more than 0x7F00 sequences
         self.prefix = bytes(prefix)                          # a raw-content prefix the frame is written against (ZSTD_CCtx_refPrefix): offsets reach into it
+        self.dict = dictionary                               # a Dictionary (make_dictionary): its content is the prefix, the frame starts from its tree, tables, offsets
+        if dictionary is not None:
+            assert not prefix
+            self.prefix = dictionary.content
+        self.bfeat = set()                                   # dictionary features of the block being written (they count once the block is kept)
         self.max_blocks, self.max_seq, self.max_lit = max_blocks, max_seq, max_lit
         self.features = set()
         self.shared, self.max_ll, self.max_ml = shared_tables, max_ll, max_ml
@@ -256,6 +274,9 @@ class FrameGen:
         else:
             desc = b""
         one = n < 1024 and (n < 8 or rng.random() < 0.4)
+        if kind == "treeless" and self.huf.block == "dict":
+            self.bfeat.add("dict_treeless")
+            if not self.comp_seen: self.bfeat.add("dict_treeless_first_%s" % ("1stream" if one else "4streams"))
         if one:
             payload = desc + self.huf.stream(lits)
             streams_fmt = [0]
@@ -300,6 +321,9 @@ class FrameGen:
             if -1 in norm: self.features.add("fse_lowprob")
             cells, desc = fse_cells(norm, al), write_ncount(norm, al)
         else: cells, al = prev; desc = b""
+        if self.dict is not None:
+            if mode != 3: self.tab_src[which] = self.block_index
+            elif self.tab_src[which] == "dict": self.bfeat.add("dict_%s_repeat" % which)
         self.tables[which] = (cells, al)
         return mode, desc, cells, al
 
@@ -333,10 +357,17 @@ class FrameGen:
             c = s[2].bit_length() - 1
             of.append((c, s[2] - (1 << c), c))
         wants, full = self.shared_wants() if self.shared else (None, None, None), (range(36), range(self.of_codes), range(53))
+        src_before = dict(self.tab_src) if self.dict is not None else {}
         m_ll, d_ll, c_ll, a_ll = self.table_for("ll", [x[0] for x in ll], 36, 5, 9, LL_DEF, 6, wants[0], full[0])
         m_of, d_of, c_of, a_of = self.table_for("of", [x[0] for x in of], 32, 5, 8, OF_DEF, 5, wants[1], full[1])
         m_ml, d_ml, c_ml, a_ml = self.table_for("ml", [x[0] for x in ml], 53, 5, 9, ML_DEF, 6, wants[2], full[2])
         self.fact.update(modes=(m_ll << 6) | (m_of << 4) | (m_ml << 2), ll_codes={x[0] for x in ll}, ml_codes={x[0] for x in ml})
+        now = {"ll": m_ll, "of": m_of, "ml": m_ml}
+        for t in now:                                        # a table of the dictionary repeated: beside what, and behind what
+            if "dict_%s_repeat" % t in self.bfeat:
+                for o in now:
+                    if o != t: self.bfeat.add("dict_%s_repeat_%s_mode%d" % (t, o, now[o]))
+                if any(src_before[o] != "dict" for o in now if o != t): self.bfeat.add("dict_table_after_redefine")
 
         def chain(cells, codes):
             """states[i] of a decoder that sees codes[i] in state i, and the bits that take it from i to i + 1"""
@@ -409,6 +440,7 @@ class FrameGen:
             else:
                 idx = ofv - 1 + (1 if ll == 0 else 0)
                 self.features.add("rep_idx%d" % idx)
+                if self.dict is not None and self.dict.formatted and not self.seq_seen and not seqs: self.bfeat.add("dict_rep_first_idx%d" % idx)
                 if idx:
                     off = rep[0] - 1 if idx == 3 else rep[idx]
                     rep = [off, rep[0], rep[1]] if idx > 1 else [off, rep[0], rep[2]]
@@ -416,6 +448,10 @@ class FrameGen:
             lits += new; out += new
             self.max_off = max(self.max_off, off)
             if off > len(out): self.features.add("off_into_prefix")
+            if self.dict is not None and off > len(out):
+                self.bfeat.add("off_into_dict")
+                if off == len(out) + len(self.prefix): self.bfeat.add("off_dict_first_byte")
+                if ml > off - len(out): self.bfeat.add("match_straddles_frame_start")
             for _ in range(ml):
                 i = len(out) - off
                 out.append(out[i] if i >= 0 else self.prefix[len(self.prefix) + i])
@@ -438,6 +474,10 @@ class FrameGen:
         while True:
             self.huf, self.tables, self.alpha = None, {}, None
             self.features = set()
+            self.tab_src, self.comp_seen, self.seq_seen = {}, 0, 0
+            if self.dict is not None and self.dict.formatted:
+                self.huf, self.tables, self.alpha = self.dict.huf, dict(self.dict.tables), bytes(sorted(self.dict.huf.code))
+                self.tab_src = {"ll": "dict", "of": "dict", "ml": "dict"}
             self.max_off = 0
             self.dense = self.want_dense
             exp, mant = rng.choice([0, 0, 1, 3, 7, rng.randint(0, 10)]), rng.randint(0, 7)
@@ -445,7 +485,7 @@ class FrameGen:
             window = (1 << (10 + exp)) + ((1 << (10 + exp)) >> 3) * mant
             block_max = min(window, 1 << 17)
             self.of_codes = (window + 3).bit_length()         # offset codes 0 ... log2 of the largest Offset_Value
-            out, rep = bytearray(), [1, 4, 8]
+            out, rep = bytearray(), (list(self.dict.rep) if self.dict is not None else [1, 4, 8])
             blocks, facts = [], []
             ok = True
             nblocks = rng.randint(16, 80) if self.shared else rng.randint(1, self.max_blocks)
@@ -462,13 +502,18 @@ class FrameGen:
                     v = rng.randrange(256)
                     blocks.append((1, n, bytes([v]))); out += bytes([v]) * n; self.features.add("rle"); facts.append({"type": "rle"})
                 else:
-                    snap = (len(out), list(rep), self.huf, dict(self.tables))
+                    snap = (len(out), list(rep), self.huf, dict(self.tables), dict(self.tab_src))
                     self.fact = {"type": "comp"}
+                    self.bfeat = set()
                     body, rep2 = self.compressed_block(out, rep, window, block_max)
                     if body is None:
-                        del out[snap[0]:]; rep, self.huf, self.tables = snap[1], snap[2], snap[3]
+                        del out[snap[0]:]; rep, self.huf, self.tables, self.tab_src = snap[1], snap[2], snap[3], snap[4]
                         continue
                     rep = rep2
+                    if self.dict is not None:
+                        if not self.comp_seen and blocks and any(x.startswith("dict_") for x in self.bfeat): self.bfeat.add("dict_first_comp_not_block0")
+                        self.features |= self.bfeat
+                        self.comp_seen += 1; self.seq_seen += self.fact["nseq"]
                     blocks.append((2, len(body), body)); self.features.add("compressed"); facts.append(self.fact)
             if not blocks or self.dense: continue               # (a dense block was asked for and did not come about: window too small, ...)
             total = len(out)
@@ -480,10 +525,15 @@ class FrameGen:
                 fcs_flag = rng.choice(flags)
             else:
                 fcs_flag = rng.choice([0, 0] + [f for f, lo, hi in ((1, 256, 65791), (2, 0, (1 << 32) - 1), (3, 0, (1 << 64) - 1)) if lo <= total <= hi])
-            did = rng.choice([0, 0, 0, 1, 2, 3])              # a Dictionary_ID field of 1 / 2 / 4 bytes holding 0 = "no dictionary" (RFC 8878 3.1.1.1.3)
+            if self.dict is None:
+                did, idv = rng.choice([0, 0, 0, 1, 2, 3]), 0  # a Dictionary_ID field of 1 / 2 / 4 bytes holding 0 = "no dictionary" (RFC 8878 3.1.1.1.3)
+            else:                                            # no field, or one of any width that holds the dictionary's ID
+                idv = self.dict.id
+                did = rng.choice([0] + [f for f, w in ((1, 1), (2, 2), (3, 4)) if idv < (1 << (8 * w))])
+                self.features.add("did_width%d" % (0, 1, 2, 4)[did] if did else "did_absent")
             unused = 0x10 if rng.random() < 0.2 else 0         # Unused_Bit: a decoder shall not interpret it
             fhd = (fcs_flag << 6) | (0x20 if single else 0) | unused | (4 if cks else 0) | did
-            hdr = bytes.fromhex("28B52FFD") + bytes([fhd]) + (b"" if single else bytes([(exp << 3) | mant])) + bytes((0, 1, 2, 4)[did])
+            hdr = bytes.fromhex("28B52FFD") + bytes([fhd]) + (b"" if single else bytes([(exp << 3) | mant])) + (idv if did else 0).to_bytes((0, 1, 2, 4)[did], "little")
             if did: self.features.add("did_field")
             if unused: self.features.add("unused_bit")
             if single and fcs_flag == 0: hdr += bytes([total])
@@ -496,6 +546,77 @@ class FrameGen:
                 body += ((n << 3) | (t << 1) | (1 if i + 1 == len(blocks) else 0)).to_bytes(3, "little") + payload
             self.facts = facts
             return bytes(hdr + body), bytes(out), cks, set(self.features)
+
+
+class Dictionary:
+    """what make_dictionary returns beside the bytes: the model a frame written against the dictionary starts from.
+    formatted (False: raw content, every byte is content and nothing else is lent), id, content, content_offset, rep (three offsets),
+    huf (a HufCode whose `block` is "dict"), huf_form ("direct" | "fse"), tables {"ll" | "of" | "ml": (cells, accuracy log)},
+    norms {"ll" | "of" | "ml": normalised counts}, spans {"huf" | "of" | "ml" | "ll" | "rep": (offset, length) in the bytes}"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def raw_dictionary(content):
+    """-> (bytes, Dictionary) of a raw-content dictionary: ID 0, no tables, repeat offsets 1 / 4 / 8"""
+    content = bytes(content)
+    assert len(content) < 8 or content[:4] != bytes.fromhex("37A430EC")
+    return content, Dictionary(formatted=False, id=0, content=content, content_offset=0, rep=(1, 4, 8), huf=None, huf_form=None, tables={}, norms={}, spans={})
+
+
+DICT_SIZES = (1, 7, 8, 9)
+
+
+def make_dictionary(seed, dict_id=None, content_size=None, alphabet=None, weights=None, depth=None, als=None, reps=None, wide=False):
+    """-> (bytes, Dictionary): a formatted dictionary (RFC 8878 5) nobody trained -- magic, Dictionary_ID, a Huffman tree description, FSE
+    descriptions of the Offset, Match_Length and Literals_Length codes in that order, three repeat offsets, content -- with everything drawn:
+      ID        0, below 256, below 65 536, any 32-bit value
+      tree      2 ... 256 symbols, depth <= 11, weights direct (symbols below 129 then) or FSE-compressed
+      tables    random_norm over any legal accuracy log (OF 5 ... 8, ML and LL 5 ... 9), "less than 1" entries, absent symbols
+      offsets   1, the content size, anything between, equal ones
+      content   1, 7, 8, 9, a few hundred bytes, a few KiB, more than 128 KiB of random bytes
+    Keywords pin a draw: dict_id, content_size, alphabet (number of symbols), weights ("direct" | "fse"), depth (of the tree),
+    als ({"ll" | "of" | "ml": accuracy log}), reps (three offsets), wide (every table covers every code its accuracy log has room for:
+    with logs of 6 and more a frame can say Repeat_Mode whatever it holds)."""
+    rng = random.Random(0x5EED0000 + seed)
+    r = rng.random()
+    idv = 0 if r < 0.04 else rng.randint(1, 255) if r < 0.3 else rng.randint(256, 65535) if r < 0.55 else rng.randint(65536, (1 << 32) - 1)
+    if dict_id is not None: idv = dict_id
+    n = rng.choice(list(DICT_SIZES) + [rng.randint(100, 900)] * 4 + [rng.randint(1024, 8192)] * 4 + [rng.randint((1 << 17) + 1, 200000)])
+    if content_size is not None: n = content_size
+    content = rng.randbytes(n)
+    form = weights or rng.choice(["direct", "fse"])
+    for _ in range(4000):
+        nsym = alphabet or rng.choice([2, 3, rng.randint(4, 20), rng.randint(20, 128), rng.randint(129, 255), 256])
+        pool = 129 if form == "direct" else 256
+        if depth is not None and alphabet is None: nsym = max(nsym, 40)
+        nsym = min(nsym, pool)
+        huf = HufCode(rng, rng.sample(range(pool), nsym))
+        if depth is not None and huf.maxbits != depth: continue
+        d = huf.description(rng, form)
+        if d is not None: break
+    else:
+        raise AssertionError("no tree description for these keywords")
+    huf.block = "dict"
+    tables, norms, descs = {}, {}, {}
+    for which, nsym, hi in (("of", 32, 8), ("ml", 53, 9), ("ll", 36, 9)):
+        al = (als or {}).get(which) or rng.randint(5, hi)
+        cap = min(nsym, (1 << al) - 1)
+        top = cap if which != "of" else min(cap, rng.randint(20, 31))      # (offset codes: at least what a window of a few MiB needs)
+        used = range(top) if rng.random() < 0.7 else rng.sample(range(nsym), rng.randint(1, cap))
+        if wide: used = range(cap)
+        norm, al = random_norm(rng, used, nsym, al, al)
+        tables[which], norms[which], descs[which] = (fse_cells(norm, al), al), norm, write_ncount(norm, al)
+    if reps is None:
+        reps = [rng.choice([1, n, rng.randint(1, n), rng.randint(1, min(n, 16))]) for _ in range(3)]
+        if rng.random() < 0.2: reps[rng.randrange(3)] = reps[rng.randrange(3)]
+    assert all(1 <= x <= n for x in reps)
+    out, spans = bytearray(bytes.fromhex("37A430EC") + struct.pack("<I", idv)), {}
+    for name, piece in (("huf", d[0]), ("of", descs["of"]), ("ml", descs["ml"]), ("ll", descs["ll"]), ("rep", struct.pack("<3I", *reps))):
+        spans[name] = (len(out), len(piece)); out += piece
+    return bytes(out) + content, Dictionary(formatted=True, id=idv, content=content, content_offset=len(out), rep=tuple(reps), huf=huf, huf_form=d[1],
+                                            tables=tables, norms=norms, spans=spans)
 
 
 def generate(seed, xxh64=None, stats=False, **kw):

@@ -45,6 +45,11 @@ static inline uint32_t zk_dict_parse(const uint8_t *d, size_t len, ZkDictLayout 
         uint32_t n = 0, mb = 0;
         const uint32_t r = zk_huf_read_weights(d + p, left(), &hd, &tmp, &n, &mb);
         if (!r) return ZK_E_DICT_CORRUPTED;
+        // HUF_readStats: a Huffman tree's deepest leaves come in pairs, so the symbols of weight 1 are two at least and even in number.
+        // The lane code builds a table from other weights too (weights 2, 2 decode like 1, 1); libzstd does not load such a dictionary.
+        uint32_t ones = 0;
+        for (uint32_t i = 0; i < n; i++) ones += hd.weights[i] == 1;
+        if (ones < 2 || (ones & 1)) return ZK_E_DICT_CORRUPTED;
         L.huf_off = (uint32_t)p; L.huf_len = r; p += r;
     }
     const int order[3] = {ZK_TAB_OF, ZK_TAB_ML, ZK_TAB_LL};
