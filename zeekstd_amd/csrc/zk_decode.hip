@@ -143,7 +143,7 @@ __global__ __launch_bounds__(1024) void zk_k_scan(const ZkFrameInfo *infos, uint
 // at a time.  The chain per symbol is shift -> LDS cell -> shift; more decoders per CU do not buy much (a pool of 4 096 / 2 560 cells,
 // 9 / 11 workgroups per CU: 2.82 -> 2.63 / 2.69 ms, profiles/r06f_huf_pool_probe.txt).  Beside zk_k_fse_predef_fed, whose 2 048
 // workgroups fill every CU's LDS in one round, this kernel waits for them to end: zk_k_entropy_frame below.
-constexpr int ZK_HUF_BLOCKS = 16;
+// (ZK_HUF_BLOCKS = 16: zk_dec_plan.h)
 constexpr uint32_t ZK_HUF_POOL = 8192;           // u16 cells
 constexpr int32_t ZK_HUF_AHEAD = 192;            // bytes the companion wave stays ahead of a stream's read position
 static_assert(ZK_HUF_POOL >= 2048, "a maximum-depth table must fit");
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(64 * (2 * ZK_FSE_WAVES + 1)) void zk_k_fse_quad(con
 // walk in lock step so that the 8-B records can be stored cooperatively (ZkCoopFlush: fewer, fuller L2 write requests,
 // which were 40% of the kernel's time).  A reference with own tables that fewer than ZK_FSEP_MIN_SHARE lanes share is not
 // worth a lock-stepped wave (archives written by libzstd: every block its own tables): the workgroup leaves at once.
-constexpr int ZK_FSEP_LANES = 64;                        // blocks per workgroup (one wave)
+// (ZK_FSEP_LANES = 64, blocks per workgroup -- one wave: zk_dec_plan.h)
 constexpr int ZK_FSEP_RING = 8;                          // records per lane between two cooperative flushes (8 x 8 B = one 64-B burst; 128-B bursts measured slower)
 constexpr uint32_t ZK_FSEP_MIN_SHARE = 8;
 constexpr uint32_t ZK_KEY_PREDEF = 0xFFFFFFFEu;
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(ZK_FSEP_LANES) void zk_k_fse_predef(const uint8_t *
 }
 
 // The same with a feeder wave: wave 0 walks (reader ZkRevL: stream words out of an LDS ring, no global load in the
-// walking wave), wave 1 feeds the ring lane for lane.  Used when the device is full of walkers (zk_launch_fse).
+// walking wave), wave 1 feeds the ring lane for lane.  Used when the device is full of walkers (zk_entropy_plan).
 // (Measured and dropped, round 6: TWO walker waves of 32 lanes each -- blocks 0..31 and 32..63 of the workgroup -- instead of one of 64, so
 //  that four half-busy walker waves interleave on a SIMD where two full ones leave its vector unit 46 % busy (profiles/r06_pmc_entropy.txt);
 //  a wave with 32 lanes at work takes two passes of the SIMD per instruction.  Six waves per SIMD need 80 registers (85 without the
@@ -1008,7 +1008,7 @@ __device__ __forceinline__ void zk_publish(uint64_t *word, uint32_t bytes, uint6
 //  256-lane tiles with a ring of 4 T 17.06 -> 17.78 ms; level 1: 9.39 -> 9.55 / 9.46 -> 9.65 ms.  Slower everywhere: the executor does
 //  not sit waiting for those lines -- five workgroups per CU cover each other's misses -- it is the NUMBER of lines that costs
 //  (profiles/r05_ref3_pmc_fetch_write.txt: 23 GiB fetched for 4 GiB of output), and a touch that is evicted before its gather fetches
-//  the line twice.  What did help there: fewer frames resident, zk_launch_exec.  profiles/r06_l3_far_touch_probe.txt.
+//  the line twice.  What did help there: fewer frames resident, zk_exec_plan.  profiles/r06_l3_far_touch_probe.txt.
 //  A first form of the touch -- a byte load into a "sink" register -- faulted: the compiler reuses a register it does not know a load
 //  is still going to write.)
 #ifndef ZK_EXEC_WIDE
@@ -1035,7 +1035,7 @@ __global__ __launch_bounds__(T) ZK_EXEC_WPE(T) void zk_k_exec(const uint8_t *__r
     // the marking pass, written into the retired slots once the slot pass no longer reads them: the fetch (an HBM round
     // trip that used to open every tile, in front of a barrier, for twice the records a tile needs) is off the critical
     // path and every record is read once.
-    constexpr int CAP = CAPX * T;                // 2 T records; 4 T where sequences are dense (zk_launch_exec)
+    constexpr int CAP = CAPX * T;                // 2 T records; 4 T where sequences are dense (zk_exec_plan)
     constexpr uint32_t M = CAP - 1;
     constexpr int NPF = CAP / T;                 // records a lane may have to fetch per tile
     __shared__ __attribute__((aligned(16))) ZkSeq S[CAP];
@@ -2668,151 +2668,92 @@ void zk_launch_huf(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_
     if (!nblocks) return;
     hipLaunchKernelGGL(zk_k_huf, dim3((nblocks + ZK_HUF_BLOCKS - 1) / ZK_HUF_BLOCKS), dim3(128), 0, st, comp, blocks, nblocks, lit);
 }
-static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, bool always);
-// which shared-table kernel a batch gets (zk_launch_fse); 0: none, the batch is small and every block takes a quad of lanes
-static int zk_fse_shared_kernel(uint32_t nblocks, const ZkKernelChoice &k, uint32_t frames)
-{
-    const uint32_t wgs = (nblocks + ZK_FSEP_LANES - 1) / ZK_FSEP_LANES;
-    if (k.fse_own == 0 && k.fse_shared == 0 && nblocks <= 16u * 256u) return 0;
-    return k.fse_shared ? k.fse_shared : (frames && (uint64_t)nblocks < 64ull * frames) ? 3 : wgs >= 6 * 256 ? 2 : 1;
-}
-// Literals and sequences in ONE kernel (zk_k_entropy_frame) where zk_launch_fse would run zk_k_fse_predef_fed over a batch whose frames
-// each define at most one set of tables (this engine's encoder); k.entropy == 2 asks for it whatever the batch's size.  false: not
-// launched, the caller runs zk_launch_huf || zk_launch_fse.
-bool zk_entropy_fused_wanted(uint32_t nblocks, uint32_t n_own_tables, const ZkKernelChoice &k, uint32_t frames)
-{
-    if (!nblocks || k.entropy == 1 || k.fse_own || n_own_tables > frames) return false;
-    if (k.entropy == 2) return k.fse_shared == 0 || k.fse_shared == 2;
-    return ZK_ENTROPY_FUSED_DEFAULT && zk_fse_shared_kernel(nblocks, k, frames) == 2;
-}
-void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, uint8_t *lit, const ZkKernelChoice &k, bool rest_always)
+// The launchers below decide nothing: the plans of zk_dec_plan.h name the kernel and its template instance, and a case's template
+// arguments are its label's literals.
+static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, ZkSeqP *seqs, ZkFseRest rest);
+void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, ZkSeqP *seqs, uint8_t *lit, const ZkEntropyPlan &p)
 {
     hipLaunchKernelGGL(zk_k_entropy_frame, dim3((nblocks + ZK_FSEP_LANES - 1) / ZK_FSEP_LANES), dim3(4 * ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs, lit);
-    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k, rest_always);
+    zk_launch_fse_rest(st, comp, blocks, nblocks, seqs, p.rest);
 }
-void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, uint32_t frames, bool rest_always)
+void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, ZkSeqP *seqs, const ZkEntropyPlan &p)
 {
-    if (!nblocks) return;
-    const int own_kernel = k.fse_own;
-    // reader choice (zk_device.h): with >= 6 workgroups per CU the memory pipeline is the limit (aligned words, each
-    // loaded once); below that a lane's instruction count is (one unaligned load per sequence).  Measured crossover
-    // on 32 KiB blocks between 1024 and 2048 frames of 2 MiB.
     const uint32_t wgs = (nblocks + ZK_FSEP_LANES - 1) / ZK_FSEP_LANES;
-    // a small batch (a seek, a handful of frames) is all chain latency: every block, predefined tables or not, takes a
-    // quad of lanes (each block builds its own copy of the tables: microseconds)
-    if (own_kernel == 0 && k.fse_shared == 0 && nblocks <= 16u * 256u) {
-        // ... and while 8-block workgroups (8-byte cells: ~63 instead of ~80 instructions per sequence of a chain, 10 KiB of tables per
-        // block, one workgroup per CU) hold every block in one round, those (what the small path's kernel runs: zk_k_small_entropy)
-        if (nblocks <= 8u * 256u) hipLaunchKernelGGL((zk_k_fse_quad<ZkCells64, 8, 1>), dim3((nblocks + 7) / 8), dim3(192), 0, st, comp, blocks, nblocks, seqs, 1u);
-        else hipLaunchKernelGGL((zk_k_fse_quad<ZkCellsX16, 16, 1>), dim3((nblocks + 15) / 16), dim3(192), 0, st, comp, blocks, nblocks, seqs, 1u);
-        return;
-    }
-    // blocks that share their tables with their neighbours (predefined, or one set per frame): one lane each
-    // frames of fewer than 64 blocks: a workgroup's 64 blocks span several frames = several table sets
-    const int shared = zk_fse_shared_kernel(nblocks, k, frames);
-    if (shared == 3) hipLaunchKernelGGL(zk_k_fse_sets, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
-    else if (shared == 2) hipLaunchKernelGGL(zk_k_fse_predef_fed, dim3(wgs), dim3(2 * ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
-    else hipLaunchKernelGGL(zk_k_fse_predef<ZkRevU>, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
-    zk_launch_fse_rest(st, comp, blocks, nblocks, n_own_tables, seqs, k, rest_always);
+    if (p.quads == 8) hipLaunchKernelGGL((zk_k_fse_quad<ZkCells64, 8, 1>), dim3((nblocks + 7) / 8), dim3(192), 0, st, comp, blocks, nblocks, seqs, 1u);
+    else if (p.quads == 16) hipLaunchKernelGGL((zk_k_fse_quad<ZkCellsX16, 16, 1>), dim3((nblocks + 15) / 16), dim3(192), 0, st, comp, blocks, nblocks, seqs, 1u);
+    else if (p.shared == 3) hipLaunchKernelGGL(zk_k_fse_sets, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
+    else if (p.shared == 2) hipLaunchKernelGGL(zk_k_fse_predef_fed, dim3(wgs), dim3(2 * ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
+    else if (p.shared == 1) hipLaunchKernelGGL(zk_k_fse_predef<ZkRevU>, dim3(wgs), dim3(ZK_FSEP_LANES), 0, st, comp, blocks, nblocks, seqs);
+    zk_launch_fse_rest(st, comp, blocks, nblocks, seqs, p.rest);
 }
-// The pass behind the shared-table kernel (zk_launch_fse, zk_launch_entropy): the blocks it has not marked done.
-// always: run it although no block of the batch defines a table -- blocks that repeat a loaded dictionary's tables define none, yet a workgroup
-// of the shared-table kernel may leave them to this pass (a block that mixes the dictionary's tables with predefined ones matches no neighbour)
-static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, bool always)
+// The pass behind the shared-table kernel or zk_k_entropy_frame: the blocks they have not marked done.
+static void zk_launch_fse_rest(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, ZkSeqP *seqs, ZkFseRest rest)
 {
-    const int own_kernel = k.fse_own;
-    // blocks with their own tables (every block is visited, the others return at once): a quad of lanes per block.
-    // While everything fits in one round, small workgroups (16 blocks, one walking wave + the toucher: 45 KiB of LDS,
-    // three per CU) spread the blocks over the CUs and a block's chain latency is all that counts (measured, 2048
-    // blocks of ~10 k sequences: 4.13 ms; 56-block workgroups 4.41; one lane per block 4.57).  Beyond that, 56 blocks
-    // per CU on four waves (32768 blocks: 20.6 ms with one lane per block, 13.2 with quads).
-    // own_kernel: zk_engine_set_fse_kernel (1 = the lane-per-block kernel, 2 = quads in the large layout).
-    if (!n_own_tables && !always) return;   // no block defines a table: everything was shared (predefined)
-    if (own_kernel == 1) { hipLaunchKernelGGL((zk_k_fse<ZkCells16, 56, 8>), dim3((nblocks + 55) / 56), dim3(512), 0, st, comp, blocks, nblocks, seqs); return; }
-    // (every block the shared-table kernel has not marked done is taken, predefined tables or not.  n_own_tables counts the
-    // DEFINING blocks: an archive of this engine's encoder has one per frame, its blocks were all shared, and the pass that
-    // finds nothing left must not wait for a whole CU's LDS -- the small layout fits beside whatever else is resident)
-    if (own_kernel != 2 && n_own_tables <= 48u * 256u)
-        hipLaunchKernelGGL((zk_k_fse_quad<ZkCellsX16, 16, 1>), dim3((nblocks + 15) / 16), dim3(192), 0, st, comp, blocks, nblocks, seqs, 1u);
-    else
-        hipLaunchKernelGGL((zk_k_fse_quad<ZkCellsX16, 56, 4>), dim3((nblocks + 55) / 56), dim3(576), 0, st, comp, blocks, nblocks, seqs, 1u);
+    switch (rest) {
+    case ZK_FSE_REST_NONE: break;
+    case ZK_FSE_REST_LANE_56x8: hipLaunchKernelGGL((zk_k_fse<ZkCells16, 56, 8>), dim3((nblocks + 55) / 56), dim3(512), 0, st, comp, blocks, nblocks, seqs); break;
+    case ZK_FSE_REST_QUAD_16x1: hipLaunchKernelGGL((zk_k_fse_quad<ZkCellsX16, 16, 1>), dim3((nblocks + 15) / 16), dim3(192), 0, st, comp, blocks, nblocks, seqs, 1u); break;
+    case ZK_FSE_REST_QUAD_56x4: hipLaunchKernelGGL((zk_k_fse_quad<ZkCellsX16, 56, 4>), dim3((nblocks + 55) / 56), dim3(576), 0, st, comp, blocks, nblocks, seqs, 1u); break;
+    }
 }
 void zk_launch_exec(hipStream_t st, const uint8_t *comp, const uint64_t *d_off, uint32_t first, uint32_t count,
                     const uint32_t *ids, const uint64_t *out_off, const ZkBlock *blocks, const ZkFrameBase *bases, ZkFrameInfo *infos, const ZkSeqP *seqs,
-                    const uint8_t *lit, uint8_t *dst, const uint8_t *prefix, uint64_t plen, const ZkKernelChoice &k, bool dense, uint64_t *progress, const uint32_t *rep_init)
+                    const uint8_t *lit, uint8_t *dst, const uint8_t *prefix, uint64_t plen, const ZkExecPlan &p, uint64_t *progress, const uint32_t *rep_init)
 {
     const ZkRepInit rep0 = {{rep_init ? rep_init[0] : 1u, rep_init ? rep_init[1] : 4u, rep_init ? rep_init[2] : 8u}};
-    // one workgroup per frame: the tile width trades bytes in flight per frame against workgroups per CU
-    // (measured on 2 MiB frames: 2048 frames -> 256 lanes.  128 lanes run the kernel alone in 8.9 instead of 9.5 ms -- eight
-    // 2-wave workgroups per CU hold all 2048 frames in one round -- but leave no room for the neighbouring batch: with two
-    // batches in flight the step is 18.8 ms against 17.2.  1024 frames: 256 lanes 4.95 ms, 128 lanes 6.9; 512 -> 512, 128 -> 1024)
-#define ZK_EXEC_LAUNCH(TT, PP, CC) hipLaunchKernelGGL((zk_k_exec<TT, PP, CC>), dim3(count), dim3(TT), (TT) == 256 ? pad : 0, st, comp, d_off, first, ids, out_off, blocks, bases, infos, seqs, lit, dst, prefix, plen, progress, rep0)
-    // ... and what a frame's matches reach: dense sequence streams (fewer than 10 output bytes per sequence: libzstd from level 3 up, whose
-    // window is the whole 2 MiB frame -- every far match a line from beyond the L2) run better with FEWER frames resident: 512-lane tiles
-    // hold 512 frames' histories live instead of 1 280 (4 GiB of the reference's level-3 frames: executor 17.0 -> 15.6 ms, the step with
-    // two batches in flight 30.6 -> 29.5 ms; level 1, whose matches stay near: 8.4 -> 9.3 ms -- hence only there; tools/gpu_calls/r6a.sh, r6n.sh)
-    const int lanes = k.exec_lanes ? k.exec_lanes : count >= 1024 ? (dense ? 512 : 256) : count >= 256 ? 512 : 1024;
-    // 93 registers and 31 000 bytes of LDS: five 256-lane workgroups per CU.  Four of them leave 128 registers on every SIMD (room for
-    // checksum waves, zk_k_xxh64_follow); a launch that asks for 2.5 KiB more LDS than the kernel uses gets four
-    const uint32_t pad = k.exec_resident == 4 ? 2560u : 0u;
-    if (prefix && plen) {
-        if (lanes <= 256) ZK_EXEC_LAUNCH(256, true, 2); else if (lanes == 512) ZK_EXEC_LAUNCH(512, true, 2); else ZK_EXEC_LAUNCH(1024, true, 2);
-        return;
+#define ZK_EXEC_LAUNCH(TT, PP, CC) hipLaunchKernelGGL((zk_k_exec<TT, PP, CC>), dim3(count), dim3(TT), p.lds_pad, st, comp, d_off, first, ids, out_off, blocks, bases, infos, seqs, lit, dst, prefix, plen, progress, rep0)
+    if (prefix && plen) switch (p.lanes) {
+        case 256: ZK_EXEC_LAUNCH(256, true, 2); break;
+        case 512: ZK_EXEC_LAUNCH(512, true, 2); break;
+        case 1024: ZK_EXEC_LAUNCH(1024, true, 2); break;
+    } else if (p.lanes == 256 && p.ring == 4) ZK_EXEC_LAUNCH(256, false, 4);
+    else switch (p.lanes) {
+        case 128: ZK_EXEC_LAUNCH(128, false, 2); break;
+        case 256: ZK_EXEC_LAUNCH(256, false, 2); break;
+        case 512: ZK_EXEC_LAUNCH(512, false, 2); break;
+        case 1024: ZK_EXEC_LAUNCH(1024, false, 2); break;
     }
-    // fewer than 10 output bytes per sequence (libzstd from level 3 up: ~8): a ring of 2 T records ends most 4 KiB tiles
-    // early; 4 T keep them whole (executor -8.5 % there, +2 % on sparser streams, hence the switch)
-    const bool ring4 = lanes == 256 && (k.exec_ring ? k.exec_ring == 2 : (count >= 1024 && dense));
-    if (ring4) ZK_EXEC_LAUNCH(256, false, 4);
-    else if (lanes == 128) ZK_EXEC_LAUNCH(128, false, 2);
-    else if (lanes == 256) ZK_EXEC_LAUNCH(256, false, 2);
-    else if (lanes == 512) ZK_EXEC_LAUNCH(512, false, 2);
-    else ZK_EXEC_LAUNCH(1024, false, 2);
 #undef ZK_EXEC_LAUNCH
 }
 void zk_launch_exec_seg(hipStream_t st, const uint8_t *comp, const uint64_t *d_off, uint32_t first, uint32_t count,
                         const uint32_t *ids, const uint64_t *out_off, const ZkBlock *blocks, const ZkFrameBase *bases, ZkFrameInfo *infos, const ZkSeqP *seqs,
-                        const uint8_t *lit, uint8_t *dst, const ZkSegScratch &sg, const ZkKernelChoice &k, bool dense, uint64_t *progress)
+                        const uint8_t *lit, uint8_t *dst, const ZkSegScratch &sg, const ZkExecSegPlan &p, uint64_t *progress)
 {
     hipLaunchKernelGGL(zk_k_seg_prep, dim3(count), dim3(64), 0, st, blocks, bases, infos, d_off, first, ids, sg.seg_bytes, sg.segs, sg.nsegs, sg.max_segs);
-    // a segment is a workgroup: wide tiles while the segments alone do not fill the device (a lone frame of 2 MiB: 16 segments), the
-    // executor's 256 lanes beyond that
-    const uint64_t wgs = (uint64_t)count * sg.max_segs;
-    const int lanes = k.exec_lanes == 256 || k.exec_lanes == 1024 ? k.exec_lanes : wgs >= 1024 ? 256 : 1024;
-    const dim3 grid(count, sg.max_segs);
+    const dim3 grid(count, sg.max_segs);                    // a segment is a workgroup
 #define ZK_SEG_LAUNCH(TT, CC) hipLaunchKernelGGL((zk_k_exec_seg<TT, CC>), grid, dim3(TT), 0, st, comp, d_off, first, ids, out_off, blocks, bases, infos, seqs, lit, dst, \
                                                  sg.segs, sg.nsegs, sg.max_segs, sg.holes, sg.tilecnt, sg.segn)
-    if (lanes == 1024) ZK_SEG_LAUNCH(1024, 2);
-    else if (k.exec_ring ? k.exec_ring == 2 : dense) ZK_SEG_LAUNCH(256, 4);
-    else ZK_SEG_LAUNCH(256, 2);
+    switch (p.lanes) {
+    case 1024: ZK_SEG_LAUNCH(1024, 2); break;
+    case 256: if (p.ring == 4) ZK_SEG_LAUNCH(256, 4); else ZK_SEG_LAUNCH(256, 2); break;
+    }
 #undef ZK_SEG_LAUNCH
-    if (k.seg_fill ? k.seg_fill == 2 : count >= 512) hipLaunchKernelGGL((zk_k_exec_fill<256>), dim3(count), dim3(256), 0, st, d_off, first, ids, out_off, bases, infos, dst, sg.segs, sg.nsegs, sg.max_segs, sg.holes, sg.tilecnt, sg.segn, progress);
-    else if (k.seg_fill == 1) hipLaunchKernelGGL((zk_k_exec_fill<1024>), dim3(count), dim3(1024), 0, st, d_off, first, ids, out_off, bases, infos, dst, sg.segs, sg.nsegs, sg.max_segs, sg.holes, sg.tilecnt, sg.segn, progress);
-    else hipLaunchKernelGGL((zk_k_exec_fill_lds<1024>), dim3(count), dim3(1024), 0, st, d_off, first, ids, out_off, bases, infos, dst, sg.segs, sg.nsegs, sg.max_segs, sg.holes, sg.tilecnt, sg.segn, progress);
+#define ZK_FILL_LAUNCH(KERNEL, TT) hipLaunchKernelGGL((KERNEL<TT>), dim3(count), dim3(TT), 0, st, d_off, first, ids, out_off, bases, infos, dst, sg.segs, sg.nsegs, sg.max_segs, sg.holes, sg.tilecnt, sg.segn, progress)
+    if (!p.fill_lds) switch (p.fill_lanes) {
+        case 256: ZK_FILL_LAUNCH(zk_k_exec_fill, 256); break;
+        case 1024: ZK_FILL_LAUNCH(zk_k_exec_fill, 1024); break;
+    } else ZK_FILL_LAUNCH(zk_k_exec_fill_lds, 1024);
+#undef ZK_FILL_LAUNCH
     // frames a segment gave up on (more hole records than its region holds): executed again, a workgroup per frame
     hipLaunchKernelGGL((zk_k_exec<256, false, 2, true>), dim3(count), dim3(256), 0, st, comp, d_off, first, ids, out_off, blocks, bases, infos, seqs, lit, dst,
                        (const uint8_t *)nullptr, (uint64_t)0, (uint64_t *)nullptr, ZkRepInit{{1u, 4u, 8u}});
 }
 void zk_launch_xxh64(hipStream_t st, const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count,
-                     ZkFrameInfo *infos, uint64_t *hashes, const ZkKernelChoice &k, const uint64_t *skip, uint32_t wide_from, bool beside)
+                     ZkFrameInfo *infos, uint64_t *hashes, const ZkXxhPlan &p, const uint64_t *skip)
 {
-    // a large batch: sixteen frames per wave (the chains' latency is the same, the instruction slots a sixteenth).  From how many frames:
-    // the decoder's pass runs alone on the device or beside a neighbour's entropy stage -- 512 frames of 2 MiB: a wave per frame 5.3 / 6.5 ms
-    // per step against 5.9 / 7.6 (two batches in flight / one at a time), hence 1024; the encoder's runs beside its matcher, which pays for
-    // every instruction slot the checksums take -- measured from 512 frames in round 3, and left there
-    // (r6) the decoder's large batches: FOUR frames per workgroup, sixteen chains in one wave fed by another (zk_k_xxh64_fed<4>: 1.65 instead
-    // of 2.7 ms per 2 MiB frame, three times the instructions); the encoder's pass, beside its entropy stage and shorter than it either way,
-    // keeps sixteen frames per wave; 2 / 3 pin the earlier forms for the tests and the probes
-    if (!skip && k.xxh == 3) hipLaunchKernelGGL(zk_k_xxh64_lean, dim3((count + 15) / 16), dim3(64), 0, st, data, d_off, first, count, infos, hashes);
-    else if (k.xxh == 2 || (beside && k.xxh == 0 && count >= wide_from)) hipLaunchKernelGGL(zk_k_xxh64_wide, dim3((count + 15) / 16), dim3(64), 0, st, data, d_off, first, count, infos, hashes, skip);
-    else if (skip || k.xxh >= 4 || (k.xxh == 0 && count >= wide_from)) hipLaunchKernelGGL(zk_k_xxh64_fed<4>, dim3((count + 3) / 4), dim3(128), 0, st, data, d_off, first, count, infos, hashes, skip);
-    else hipLaunchKernelGGL(zk_k_xxh64, dim3(count), dim3(64), 0, st, data, d_off, first, count, infos, hashes);
+    const dim3 grid((count + p.frames_per_wg - 1) / p.frames_per_wg);
+    switch (p.kernel) {
+    case ZK_XXH_FRAME: hipLaunchKernelGGL(zk_k_xxh64, grid, dim3(64), 0, st, data, d_off, first, count, infos, hashes); break;
+    case ZK_XXH_WIDE: hipLaunchKernelGGL(zk_k_xxh64_wide, grid, dim3(64), 0, st, data, d_off, first, count, infos, hashes, skip); break;
+    case ZK_XXH_LEAN: hipLaunchKernelGGL(zk_k_xxh64_lean, grid, dim3(64), 0, st, data, d_off, first, count, infos, hashes); break;
+    case ZK_XXH_FED4: hipLaunchKernelGGL(zk_k_xxh64_fed<4>, grid, dim3(128), 0, st, data, d_off, first, count, infos, hashes, skip); break;
+    }
 }
-void zk_launch_xxh64_follow(hipStream_t st, const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count, const ZkFrameInfo *infos, uint64_t *progress)
+void zk_launch_xxh64_follow(hipStream_t st, const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count, const ZkFrameInfo *infos, uint64_t *progress,
+                            const ZkXxhFollowPlan &p)
 {
-    // a handful of frames: a wave per frame (a frame's chains run 1.7 ms per 2 MiB there, 2.25 ms sixteen frames to a wave)
-    if (count <= 32) { hipLaunchKernelGGL(zk_k_xxh64_follow1, dim3(8 * ((count + 7) / 8)), dim3(64), 0, st, data, d_off, first, count, infos, progress); return; }
-    // eight waves per 128 frames: each takes the frames of one XCD
-    hipLaunchKernelGGL(zk_k_xxh64_follow, dim3(8 * ((count + 127) / 128)), dim3(64), 0, st, data, d_off, first, count, infos, progress);
+    if (p.follow1) hipLaunchKernelGGL(zk_k_xxh64_follow1, dim3(p.grid), dim3(64), 0, st, data, d_off, first, count, infos, progress);
+    else hipLaunchKernelGGL(zk_k_xxh64_follow, dim3(p.grid), dim3(64), 0, st, data, d_off, first, count, infos, progress);
 }
 
 void zk_launch_small_walk(hipStream_t st, const uint8_t *h_comp, uint64_t comp_bytes, const uint64_t *h_offs, uint32_t count, uint64_t dst_cap,

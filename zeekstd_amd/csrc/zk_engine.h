@@ -119,7 +119,7 @@ int zk_dec_ctx_ready(zk_engine *e, int slot);           // creates the context's
 inline hipStream_t zk_dec_stream(zk_engine *e, zk_engine::DecCtx &c, void *stream) { return &c == &e->dctx[0] && stream ? (hipStream_t)stream : c.st; }
 inline ZkDecShape zk_dec_shape(const zk_engine *e, uint32_t count, uint64_t out_bytes, uint64_t max_frame, uint64_t nblocks, bool has_prefix, bool alone)
 {
-    return ZkDecShape{e->choice.xxh, e->choice.exec_seg, e->choice.seg_kib, e->profiling, count, out_bytes, max_frame, nblocks, has_prefix, alone, false};
+    return ZkDecShape{e->choice, e->profiling, count, out_bytes, max_frame, nblocks, has_prefix, alone, false};
 }
 int zk_decode_enqueue(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a);
 int zk_decode_finish(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st);
@@ -135,10 +135,10 @@ int zk_dec_seg_scratch(zk_engine *e, zk_engine::DecCtx &c, uint32_t count, const
 // the checksums beside the executor: its progress words (cleared on st) and the context's second queue
 int zk_dec_follow_prepare(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, uint32_t count, uint64_t **prog);
 int zk_dec_fork(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st);     // the second queue goes on from where st is now
-// the executor (sgs: in segments; kc: its choice), ev_exec when a.mark_exec, then the checksums: zk_k_xxh64_follow on the second queue and
-// what it left when `prog` (zk_dec_follow_prepare + zk_dec_fork came first), the plain pass when a.verify, else none
-int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, const ZkSegScratch *sgs, const ZkKernelChoice &kc,
-                          bool dense, uint64_t *prog, const uint32_t *rep_init);
+// the executor (sgs: in segments; its kernels planned from shape and nseq, 0 = not known), ev_exec when a.mark_exec, then the checksums: zk_k_xxh64_follow
+// on the second queue and what it left when `prog` (zk_dec_follow_prepare + zk_dec_fork came first), the plain pass when a.verify, else none
+int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, const ZkSegScratch *sgs, const ZkDecShape &shape,
+                          uint64_t nseq, uint64_t *prog, const uint32_t *rep_init);
 // does this call decode against the engine's dictionary?  (an explicit prefix overrides it, as ZSTD_DCtx_refPrefix does)
 inline bool zk_dict_applies(const zk_engine *e, const void *d_prefix) { return e->dict.on && !d_prefix; }
 namespace zeekstd { class SeekTable; }

@@ -288,8 +288,8 @@ int zk_dec_fork(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st)
     ZK_HIP(hipStreamWaitEvent(c.aux, c.ev_fork, 0));
     return 0;
 }
-int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, const ZkSegScratch *sgs, const ZkKernelChoice &kc,
-                          bool dense, uint64_t *prog, const uint32_t *rep_init)
+int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, const ZkSegScratch *sgs, const ZkDecShape &shape,
+                          uint64_t nseq, uint64_t *prog, const uint32_t *rep_init)
 {
     const uint8_t *comp = (const uint8_t *)a.d_comp, *lit = (const uint8_t *)c.lit.p;
     uint8_t *dst = (uint8_t *)a.d_dst;
@@ -300,17 +300,18 @@ int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, co
     ZkFrameInfo *infos = (ZkFrameInfo *)c.infos.p;
     const uint64_t *x_off = a.out_off ? a.out_off : d_off;   // packed indexed output: out_off (count + 1 prefix sums) doubles as the d_off of the checksum kernels
     const uint32_t x_first = a.out_off ? 0 : a.first;
-    if (sgs) { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec_seg(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, *sgs, kc, dense, prog); }
-    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, (const uint8_t *)a.d_prefix, a.d_prefix ? a.prefix_len : 0, kc, dense, prog, rep_init); }
+    const uint64_t plen = a.d_prefix ? a.prefix_len : 0;
+    if (sgs) { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec_seg(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, *sgs, zk_exec_seg_plan(a.count, sgs->max_segs, nseq, shape.out_bytes, shape.k), prog); }
+    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, (const uint8_t *)a.d_prefix, plen, zk_exec_plan(a.count, nseq, shape.out_bytes, plen != 0, shape.follow, shape.k), prog, rep_init); }
     if (a.mark_exec) ZK_HIP(hipEventRecord(c.ev_exec, st));
     if (prog) {
         // enqueued BEHIND the executor's launch: were the two queues ever served one after the other, the checksum waves would find
         // finished frames, not wait (ZK_FOLLOW_PATIENCE) for an executor that cannot start
-        zk_launch_xxh64_follow(c.aux, dst, x_off, x_first, a.count, infos, prog);
+        zk_launch_xxh64_follow(c.aux, dst, x_off, x_first, a.count, infos, prog, zk_xxh_follow_plan(a.count));
         ZK_HIP(hipEventRecord(c.ev_join, c.aux));
         ZK_HIP(hipStreamWaitEvent(st, c.ev_join, 0));
-        zk_launch_xxh64(st, dst, x_off, x_first, a.count, infos, nullptr, e->choice, prog);
-    } else if (a.verify) { zk_kernel_timer t(e, ZK_K_XXH64, st); zk_launch_xxh64(st, dst, x_off, x_first, a.count, infos, nullptr, e->choice); }
+        zk_launch_xxh64(st, dst, x_off, x_first, a.count, infos, nullptr, zk_xxh_plan(a.count, shape.k, true), prog);
+    } else if (a.verify) { zk_kernel_timer t(e, ZK_K_XXH64, st); zk_launch_xxh64(st, dst, x_off, x_first, a.count, infos, nullptr, zk_xxh_plan(a.count, shape.k, false)); }
     return 0;
 }
 
@@ -334,9 +335,9 @@ int zk_decode_enqueue(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const 
     const uint64_t nblocks = c.h_words[ZK_SCAN_BLOCKS], nseq = c.h_words[ZK_SCAN_SEQS], nlit = c.h_words[ZK_SCAN_LITS], out_bytes = c.h_words[ZK_SCAN_OUT_BYTES];
     const uint32_t n_own = (uint32_t)c.h_words[ZK_SCAN_OWN_TABLES];
     a.verify = a.verify && c.h_words[ZK_SCAN_CHECKSUMMED] != 0;    // (a batch without a Content_Checksum: zeekstd's library default, encode.rs:163-167 -- no checksum kernel is launched)
-    // the pass behind the shared-table kernels has to run whenever a dictionary lends tables (zk_launch_fse_rest)
-    const bool rest_always = with_dict && e->dict.tables;
-    const bool dense = nseq * 10 > out_bytes;                // fewer than 10 output bytes per sequence (zk_launch_exec)
+    // the pass behind the shared-table kernels has to run whenever a dictionary lends tables (rest_always, zk_entropy_plan); no fused
+    // kernel with per-kernel timing on, nor on one queue
+    const ZkEntropyPlan ep = zk_entropy_plan((uint32_t)nblocks, n_own, count, e->choice, with_dict && e->dict.tables, e->profiling || a.single_queue);
     ZkDecShape shape = zk_dec_shape(e, count, out_bytes, c.h_words[ZK_SCAN_MAX_FRAME], nblocks, a.d_prefix != nullptr, a.alone);
     if ((rc = zk_dec_block_scratch(e, c, nblocks, nseq))) return rc;
     if ((rc = zk_devbuf_reserve(e, c.lit, (size_t)nlit + 64))) return rc;
@@ -353,8 +354,6 @@ int zk_decode_enqueue(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const 
     const ZkSegPlan sp = zk_seg_plan_dev(shape);
     ZkSegScratch sgs{};
     if (sp.on && (rc = zk_dec_seg_scratch(e, c, count, sp, out_bytes, nblocks, sgs))) return rc;
-    ZkKernelChoice kc = e->choice;
-    if (follow && !kc.exec_resident) kc.exec_resident = 4;
     uint64_t *prog = nullptr;
     if (follow && (rc = zk_dec_follow_prepare(e, c, st, count, &prog))) return rc;
     ZK_HIP(hipMemsetAsync(words + 6, 0, sizeof(uint64_t), st));
@@ -363,20 +362,20 @@ int zk_decode_enqueue(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const 
     // with per-kernel timing on they are serialised instead
     // ... or, where the sequences would get zk_k_fse_predef_fed, both in one kernel whose workgroups each bring a Huffman half and a
     // sequence half (zk_k_entropy_frame: no second queue, no events)
-    c.fused = !e->profiling && !a.single_queue && zk_entropy_fused_wanted((uint32_t)nblocks, n_own, e->choice, count);
-    if (c.fused) zk_launch_entropy(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, lit, e->choice, rest_always);
+    c.fused = ep.fused;
+    if (ep.fused) zk_launch_entropy(st, comp, blocks, (uint32_t)nblocks, seqs, lit, ep);
     else if (e->profiling || a.single_queue) {
         { zk_kernel_timer t(e, ZK_K_HUF, st); zk_launch_huf(st, comp, blocks, (uint32_t)nblocks, lit); }
-        { zk_kernel_timer t(e, ZK_K_FSE, st); zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count, rest_always); }
+        { zk_kernel_timer t(e, ZK_K_FSE, st); zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, seqs, ep); }
     } else {
         if ((rc = zk_dec_ctx_aux(e, c)) || (rc = zk_dec_fork(e, c, st))) return rc;
         zk_launch_huf(c.aux, comp, blocks, (uint32_t)nblocks, lit);
         ZK_HIP(hipEventRecord(c.ev_join, c.aux));
-        zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, n_own, seqs, e->choice, count, rest_always);
+        zk_launch_fse(st, comp, blocks, (uint32_t)nblocks, seqs, ep);
         ZK_HIP(hipStreamWaitEvent(st, c.ev_join, 0));
     }
     if (follow && (rc = zk_dec_fork(e, c, st))) return rc;  // (in front of the executor: the checksum waves start with it)
-    if ((rc = zk_dec_exec_checksums(e, c, st, a, sp.on ? &sgs : nullptr, kc, dense, prog, with_dict ? e->dict.rep : nullptr))) return rc;
+    if ((rc = zk_dec_exec_checksums(e, c, st, a, sp.on ? &sgs : nullptr, shape, nseq, prog, with_dict ? e->dict.rep : nullptr))) return rc;
     { zk_kernel_timer t(e, ZK_K_STATUS, st); zk_launch_status(st, (const ZkFrameInfo *)c.infos.p, count, (int32_t *)a.d_frame_status, words + 3, prog, words + 6); }
     ZK_HIP(hipMemcpyAsync(c.h_words + 3, words + 3, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     return 0;
@@ -542,7 +541,7 @@ extern "C" int zk_frame_content_sizes_dev(zk_engine *e, const void *d_comp, uint
     if ((rc = zk_dec_block_scratch(e, c, nblocks, c.h_words[ZK_SCAN_SEQS]))) return rc;
     zk_dec_walk(e, c, st, a, with_dict, nblocks, true);
     ZkBlock *blocks = (ZkBlock *)c.blocks.p;
-    zk_launch_fse(st, (const uint8_t *)d_comp, blocks, (uint32_t)nblocks, (uint32_t)c.h_words[ZK_SCAN_OWN_TABLES], (ZkSeqP *)c.seqs.p, e->choice, count, with_dict && e->dict.tables);
+    zk_launch_fse(st, (const uint8_t *)d_comp, blocks, (uint32_t)nblocks, (ZkSeqP *)c.seqs.p, zk_entropy_plan((uint32_t)nblocks, (uint32_t)c.h_words[ZK_SCAN_OWN_TABLES], count, e->choice, with_dict && e->dict.tables, true));   // (true: no literals here, no fused kernel)
     zk_launch_frame_sizes(st, (const ZkFrameInfo *)c.infos.p, (const ZkFrameBase *)c.bases.p, blocks, count, (uint64_t *)d_sizes, (int32_t *)d_frame_status);
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
@@ -588,7 +587,7 @@ extern "C" int zk_xxh64_frames_dev(zk_engine *e, const void *d_data, const void 
     uint64_t off0 = 0;
     ZK_HIP(hipMemcpyAsync(&off0, d_off, 8, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
-    zk_launch_xxh64(st, (const uint8_t *)d_data + off0, (const uint64_t *)d_off, 0, count, nullptr, (uint64_t *)d_out, e->choice);
+    zk_launch_xxh64(st, (const uint8_t *)d_data + off0, (const uint64_t *)d_off, 0, count, nullptr, (uint64_t *)d_out, zk_xxh_plan(count, e->choice, false));
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
     return 0;

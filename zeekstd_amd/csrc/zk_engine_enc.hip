@@ -229,10 +229,10 @@ static int zk_enc_checksums_fork(zk_engine *e, const zk_enc_args &a, ZkEncLayout
     if (!e->profiling && c.aux) {
         ZK_HIP(hipEventRecord(c.ev_fork, st));
         ZK_HIP(hipStreamWaitEvent(c.aux, c.ev_fork, 0));
-        zk_launch_xxh64(c.aux, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, e->choice, nullptr, 512, true);
+        zk_launch_xxh64(c.aux, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, zk_xxh_plan_enc(L.pl.nf, e->choice));
         ZK_HIP(hipEventRecord(c.ev_join, c.aux));
         L.cks_beside = true;
-    } else { zk_kernel_timer t(e, ZK_K_ENC_XXH64, st); zk_launch_xxh64(st, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, e->choice, nullptr, 512, true); }
+    } else { zk_kernel_timer t(e, ZK_K_ENC_XXH64, st); zk_launch_xxh64(st, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, zk_xxh_plan_enc(L.pl.nf, e->choice)); }
     return 0;
 }
 

@@ -497,7 +497,7 @@ static int zk_decode_small(zk_engine *e, zk_hostpipe *hp, const zk_host_src &src
     ZkSegScratch sgs{};
     if (sp.on && (rc = zk_dec_seg_scratch(e, c, count, sp, dsz, block_cap, sgs))) return rc;
     const zk_dec_args a{comp, csz, d_offs, d_offs + count + 1, 0, count, nullptr, nullptr, s.out.p, dsz, verify, s.st.p, d_prefix, d_prefix ? prefix_len : 0};
-    if ((rc = zk_dec_exec_checksums(e, c, st, a, sp.on ? &sgs : nullptr, e->choice, false, prog, nullptr))) return rc;
+    if ((rc = zk_dec_exec_checksums(e, c, st, a, sp.on ? &sgs : nullptr, shape, 0, prog, nullptr))) return rc;       // (0: the sequence totals stay on the device)
     zk_launch_small_publish(st, infos, d_offs, count, (const uint8_t *)s.out.p, dsz ? h_out : nullptr, (int32_t *)s.st.p, h_status, words, hp->pin_flag, gen);
     // completion: the last workgroup of the publish kernel writes the generation into pinned memory
     volatile uint32_t *flag = hp->pin_flag;

@@ -1,26 +1,11 @@
-// zk_kernels.h -- host-callable launchers of the gfx950 kernels (zk_decode.hip, zk_encode.hip, zk_ranges.hip)
+// zk_kernels.h -- host-callable launchers of the gfx950 kernels (zk_decode.hip, zk_encode.hip, zk_ranges.hip).  The decode launchers decide
+// nothing: which kernel, which template instance and how many blocks or frames per workgroup come in a plan struct of zk_dec_plan.h
+// (where ZkKernelChoice lives too), filled by the engine.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "zk_device.h"
+#include "zk_dec_plan.h"
 
-// Which kernel variant a launcher picks.  0 everywhere = by batch shape (what production runs); the other values pin one
-// variant whatever the batch looks like, so that tests/ can put every kernel of the large-batch path under a small, exhaustively
-// checked input (zk_engine_set_kernel_choice, include/zeekstd_amd.h) and tools/ can time one against the other.
-struct ZkKernelChoice {
-    int fse_own = 0;        // blocks with tables of their own: 1 zk_k_fse (a lane per block), 2 zk_k_fse_quad in the 56-block layout
-    int fse_shared = 0;     // blocks that share tables: 1 zk_k_fse_predef, 2 zk_k_fse_predef_fed, 3 zk_k_fse_sets
-    int exec_lanes = 0;     // zk_k_exec tile: 128 / 256 / 512 / 1024 lanes
-    int exec_ring = 0;      // 256-lane tiles: 1 a ring of 2 T records, 2 of 4 T
-    int xxh = 0;            // 1 zk_k_xxh64 (a wave per frame), 2 zk_k_xxh64_wide (sixteen frames per wave), 3 zk_k_xxh64_lean (the same in 64 registers),
-                            // 4 zk_k_xxh64_follow beside the executor (zk_engine.hip)
-    int exec_resident = 0;  // zk_k_exec<256>: workgroups per CU (4 / 5) through LDS the launch asks for and does not use
-    int small_path = 0;     // host-pointer decode of <= 64 frames: 1 the general pipeline instead, 2 the small path's entropy roles as two kernels
-    int exec_seg = 0;       // the executor in segments (zk_k_seg_prep / zk_k_exec_seg / zk_k_exec_fill): 1 never, 2 always (without a prefix); 0 by batch shape
-    int seg_kib = 0;        // ... output KiB per segment (1..128; 0 = 128, or 4 for short frames on the small path: zk_dec_plan.h)
-    int seg_fill = 0;       // ... the fill pass: 1 zk_k_exec_fill<1024> (rounds through memory), 2 zk_k_exec_fill<256>, 3 zk_k_exec_fill_lds (the segment's holes in LDS); 0 by batch size
-    int entropy = 0;        // literals and sequences of a batch: 1 zk_k_huf || the sequence kernels on two queues, 2 zk_k_entropy_frame wherever a batch qualifies
-                            // (zk_entropy_fused_wanted); 0 by batch shape
-};
 // scratch of the segmented executor (zk_engine.hip sizes it; zk_device.h: zk_seg_region)
 struct ZkSegScratch { ZkSeg *segs; uint32_t *nsegs, *segn; ZkHole *holes; uint32_t *tilecnt; uint32_t max_segs, seg_bytes; };
 
@@ -35,27 +20,25 @@ void zk_launch_walk(hipStream_t st, const uint8_t *comp, uint64_t comp_size, con
 void zk_launch_frame_sizes(hipStream_t st, const ZkFrameInfo *infos, const ZkFrameBase *bases, const ZkBlock *blocks, uint32_t count, uint64_t *sizes, int32_t *status_out);
 void zk_launch_scan(hipStream_t st, const ZkFrameInfo *infos, uint32_t count, ZkFrameBase *bases, uint64_t *totals, const uint64_t *d_off, uint32_t first, const uint64_t *out_off);
 void zk_launch_huf(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint8_t *lit);
-void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, const ZkKernelChoice &k, uint32_t frames = 0,
-                   bool rest_always = false);   // rest_always: the pass behind the shared-table kernel runs although n_own_tables is 0 (a dictionary's tables)
-// zk_k_entropy_frame in place of zk_launch_huf || zk_launch_fse: whether a batch gets it, and the launch (with the pass for the blocks it leaves)
-constexpr bool ZK_ENTROPY_FUSED_DEFAULT = true;
-bool zk_entropy_fused_wanted(uint32_t nblocks, uint32_t n_own_tables, const ZkKernelChoice &k, uint32_t frames);
-void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, uint32_t n_own_tables, ZkSeqP *seqs, uint8_t *lit, const ZkKernelChoice &k, bool rest_always = false);
+// the sequences of a batch: p.quads / p.shared, then p.rest (p.fused is the caller's: zk_launch_entropy in place of zk_launch_huf || zk_launch_fse)
+void zk_launch_fse(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, ZkSeqP *seqs, const ZkEntropyPlan &p);
+// zk_k_entropy_frame, then p.rest
+void zk_launch_entropy(hipStream_t st, const uint8_t *comp, ZkBlock *blocks, uint32_t nblocks, ZkSeqP *seqs, uint8_t *lit, const ZkEntropyPlan &p);
 void zk_launch_exec(hipStream_t st, const uint8_t *comp, const uint64_t *d_off, uint32_t first, uint32_t count,
                     const uint32_t *ids, const uint64_t *out_off, const ZkBlock *blocks, const ZkFrameBase *bases, ZkFrameInfo *infos, const ZkSeqP *seqs,
-                    const uint8_t *lit, uint8_t *dst, const uint8_t *prefix, uint64_t plen, const ZkKernelChoice &k, bool dense = false,
+                    const uint8_t *lit, uint8_t *dst, const uint8_t *prefix, uint64_t plen, const ZkExecPlan &p,      // p: planned with has_prefix = prefix && plen
                     uint64_t *progress = nullptr,       // progress: one word per frame for zk_launch_xxh64_follow (zk_decode.hip: zk_publish)
                     const uint32_t *rep_init = nullptr); // with a prefix: the three repeat offsets every frame starts with (a dictionary's; nullptr = 1 / 4 / 8)
 void zk_launch_exec_seg(hipStream_t st, const uint8_t *comp, const uint64_t *d_off, uint32_t first, uint32_t count,
                         const uint32_t *ids, const uint64_t *out_off, const ZkBlock *blocks, const ZkFrameBase *bases, ZkFrameInfo *infos, const ZkSeqP *seqs,
-                        const uint8_t *lit, uint8_t *dst, const ZkSegScratch &sg, const ZkKernelChoice &k, bool dense, uint64_t *progress = nullptr);
+                        const uint8_t *lit, uint8_t *dst, const ZkSegScratch &sg, const ZkExecSegPlan &p, uint64_t *progress = nullptr);
+// skip (the progress words zk_launch_xxh64_follow left): frames marked there are done -- the plan was made with skip = true
 void zk_launch_xxh64(hipStream_t st, const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count,
-                     ZkFrameInfo *infos, uint64_t *hashes, const ZkKernelChoice &k, const uint64_t *skip = nullptr,
-                     uint32_t wide_from = 1024,          // frames from which several share a workgroup (the encoder passes 512: zk_decode.hip)
-                     bool beside = false);               // the pass runs beside a kernel that pays for its instruction slots (the encoder's): sixteen frames per wave
+                     ZkFrameInfo *infos, uint64_t *hashes, const ZkXxhPlan &p, const uint64_t *skip = nullptr);
 // the checksums beside the executor that publishes `progress` (launched on another queue); frames it verifies are marked in `progress`,
 // zk_launch_xxh64(..., skip = progress) behind the executor takes the rest
-void zk_launch_xxh64_follow(hipStream_t st, const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count, const ZkFrameInfo *infos, uint64_t *progress);
+void zk_launch_xxh64_follow(hipStream_t st, const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count, const ZkFrameInfo *infos, uint64_t *progress,
+                            const ZkXxhFollowPlan &p);
 void zk_launch_status(hipStream_t st, const ZkFrameInfo *infos, uint32_t count, int32_t *status_out, uint64_t *first_err,
                       const uint64_t *progress = nullptr, uint64_t *followed = nullptr);
 
