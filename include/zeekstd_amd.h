@@ -260,13 +260,22 @@ int zk_decode_wait(zk_engine *e, int slot);
  * refreshed every 1024 instead of 4096 positions; level >= 9: 2^18 slots.  Ratio on the survey's text 2.485 / 2.655 / 2.732 /
  * 2.736 / 2.743 (libzstd 1.5.7: 2.50 at level 1, 2.79 at 3, 2.88 at 9), encode 100 / 47 / 24 / 20 / 20 GiB/s HBM to HBM.
  * Replaces the ZSTD_compressStream2 loops of encode.rs:340-346, 442-464.
- * dst_cap >= zk_compress_bound(n, frame_size) always suffices; otherwise -70 (dstSize_tooSmall) may come back.
+ * dst_cap >= zk_compress_bound(n, frame_size) always suffices; otherwise -70 (dstSize_tooSmall) may come back, and then nothing has been
+ * written to dst by the device entry points (the host ones may have delivered pieces below dst_cap).
+ * zk_compress_bound(n, frame_size) = n + frames * (6 + 4 + 3 * (ceil(frame_size / 1024) + 8)) + 16, frames = max(1, ceil(n / frame_size)); 0 for
+ * frame_size 0.  Per frame that is the header, the checksum and a 3-byte header for more blocks than the frame can have (one block up to
+ * 4 KiB, blocks of at least 4 KiB above): at least 24 bytes spare.  Blocks are stored raw unless their compressed form is smaller; only the
+ * one block that carries a frame's table descriptions (frames with >= 256 sequences) can outgrow its input, by at most 149 bytes, which the
+ * spare headers cover from 37 889 bytes of frame size on and the sequences' savings below (tests/test_encode_bound.py).
  */
 uint64_t zk_compress_bound(uint64_t n, uint32_t frame_size);
 int zk_encode_frames(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum,
                      uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint32_t frames_cap,
                      uint32_t *n_frames, uint64_t *written);
-/* Device-resident variant: d_src / d_dst / d_c_sizes / d_d_sizes (uint32 arrays, may be NULL) live in HBM. */
+/* Device-resident variant: d_src / d_dst / d_c_sizes / d_d_sizes (uint32 arrays, may be NULL) live in HBM.  Once the call has
+ * returned -- with 0, with -70 or with any other error -- no kernel of it reads d_src any more, on either of the engine's queues.
+ * With dst_cap below the bound the total decides before anything is written: -70 leaves d_dst untouched; what d_c_sizes /
+ * d_d_sizes hold after an error is unspecified. */
 int zk_encode_frames_dev(zk_engine *e, const void *d_src, uint64_t n, uint32_t frame_size, int level, int checksum,
                          void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint32_t *n_frames,
                          uint64_t *written, void *stream);

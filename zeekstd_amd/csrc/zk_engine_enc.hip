@@ -22,11 +22,17 @@ void zk_build_enc_tables(ZkEncTables *t)
     t->al[0] = 6; t->al[1] = 5; t->al[2] = 6;
 }
 
+// Per frame: header (6) + checksum (4) + a 3-byte header for more blocks than a frame can have.  A frame has one block up to 4 KiB and blocks
+// of at least 4 KiB above that (zke_block_max), so ceil(frame_size / 1024) + 8 leaves at least 8 block headers (24 bytes) spare, and three per
+// KiB from 4 KiB on.  A raw block is its input, every other block is smaller than its input (zk_k_enc_entropy: total < bsz) -- except the one
+// defining block of a frame with >= 256 sequences, which zk_k_enc_sizes grows by the table descriptions (<= 108 bytes at accuracy log 6,
+// <= 150 at 9 / 8 / 9).  The spare headers cover those from 37 889 bytes on; below that what the >= 256 sequences save does (DESIGN.md
+// 5.2f: argued and measured, not proven; tests/test_encode_bound.py).  zk_host_encode reserves exactly this much: it is not advisory.
 extern "C" uint64_t zk_compress_bound(uint64_t n, uint32_t frame_size)
 {
     if (frame_size == 0) return 0;
     const uint64_t nf = n == 0 ? 1 : (n + frame_size - 1) / frame_size;
-    const uint64_t blocks_per_frame = ((uint64_t)frame_size + 1023) / 1024 + 8;     // blocks are >= 1 KiB except in tiny frames
+    const uint64_t blocks_per_frame = ((uint64_t)frame_size + 1023) / 1024 + 8;
     return n + nf * (6 + 4 + 3 * blocks_per_frame) + 16;
 }
 
@@ -227,11 +233,11 @@ static int zk_enc_checksums_fork(zk_engine *e, const zk_enc_args &a, ZkEncLayout
             hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming) != hipSuccess) { c.aux = nullptr; (void)hipGetLastError(); }
     }
     if (!e->profiling && c.aux) {
+        L.cks_beside = true;                // from here on an early return of zk_encode_enqueue waits for the second queue
         ZK_HIP(hipEventRecord(c.ev_fork, st));
         ZK_HIP(hipStreamWaitEvent(c.aux, c.ev_fork, 0));
         zk_launch_xxh64(c.aux, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, zk_xxh_plan_enc(L.pl.nf, e->choice));
         ZK_HIP(hipEventRecord(c.ev_join, c.aux));
-        L.cks_beside = true;
     } else { zk_kernel_timer t(e, ZK_K_ENC_XXH64, st); zk_launch_xxh64(st, L.src, L.d_doff, 0, L.pl.nf, nullptr, L.hashes, zk_xxh_plan_enc(L.pl.nf, e->choice)); }
     return 0;
 }
@@ -274,6 +280,8 @@ static int zk_enc_assemble(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, h
 // the engine's pinned word ZK_HW_ENC_TOTAL once the stream has run (zk_encode_finish); a smaller destination needs the
 // total before the frames may be assembled, so the stream is synchronised once in the middle (zk_enc_fit_check).
 // The frame / block lists are built in pinned host memory that stays untouched until the next enqueue: one encode in flight.
+// A stage that refuses the call (-70 from zk_enc_fit_check, a failed reservation or launch) leaves through the loop's one exit, which waits
+// for the second queue if zk_enc_checksums_fork has put the checksums there: zk_enc_assemble, which joins them, has not run then.
 int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32_t *nf_out)
 {
     if (!e || a.frame_size == 0 || a.frame_size > ZK_SEEKABLE_MAX_FRAME_SIZE || !a.d_dst || (a.n && !a.d_src)) return ZK_ERR_ARGUMENT;
@@ -283,7 +291,12 @@ int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32
         zk_enc_plan_upload, zk_enc_stage_hist, zk_enc_far_history, zk_enc_match, zk_enc_table_build, zk_enc_checksums_fork,
         zk_enc_entropy, zk_enc_sizes_total, zk_enc_fit_check, zk_enc_assemble};
     ZkEncLayout L;
-    for (auto stage : stages) if (const int rc = stage(e, a, L, st)) return rc;
+    L.cks_beside = false;
+    for (auto stage : stages) if (const int rc = stage(e, a, L, st)) {
+        // the checksum kernel on the second queue reads the caller's source: nothing of this call runs on once it has returned
+        if (L.cks_beside) (void)hipStreamSynchronize(e->enc.aux);
+        return rc;
+    }
     if (nf_out) *nf_out = L.pl.nf;
     return 0;
 }
