@@ -238,7 +238,44 @@ int zk_frame_content_sizes_dev(zk_engine *e, const void *d_comp, uint64_t comp_s
  * two batches may be outstanding (a third submit returns ZK_ERR_ARGUMENT until the older one was waited for) and
  * all buffers of a batch must stay untouched until its wait.  The gain: the last stage of a batch (per-frame XXH64,
  * a serial chain that leaves the GPU mostly idle) overlaps the first stages of the next.  No reference counterpart:
- * zeekstd's Decoder is synchronous (lib/src/decode.rs:201-270); this is the batch engine's pipelining. */
+ * zeekstd's Decoder is synchronous (lib/src/decode.rs:201-270); this is the batch engine's pipelining.
+ *
+ * Slots ALTERNATE: the first submit of an engine gets context 0, every successful submit hands the turn to the other context, nothing else
+ * moves it.  A submit whose turn is a context that still holds a batch is refused -- also when the other context is free (submit A,
+ * submit B, wait B, submit: refused until A was waited for); DESIGN.md 5e says why.  Waits may come in any order.  zk_decode_wait on a
+ * context that holds no batch, or on a slot other than 0 and 1, is ZK_ERR_ARGUMENT.  count == 0: ZK_ERR_ARGUMENT from a submit (there
+ * would be no batch to wait for; *slot_out is not written), while zk_decode_frames_dev returns 0.  A refused or failed submit leaves the
+ * turn, *slot_out and the buffers as they were.
+ *
+ * What every other entry point does while (a) context 0, (b) context 1, (c) both hold a submitted batch:
+ *   refused   ZK_ERR_ARGUMENT at once: nothing enqueued, nothing reserved or uploaded, no wait for the batch, output buffers and the
+ *             engine's diagnostics as they were
+ *   served    the result the call has with nothing in flight, and the batches unaffected.  (It may take longer: a call that runs on
+ *             context 0's queue runs behind context 0's batch, and one that has to grow a buffer of the engine waits for the device.)
+ *
+ *                                                                                   (a)       (b)       (c)
+ *   zk_decode_frames_dev, zk_decode_frames_prefix_dev, zk_decode_frame_list_dev     refused   served    refused    (they run on context 0,
+ *   zk_frame_content_sizes_dev, zk_read_ranges_dev                                  refused   served    refused     also on the caller's stream)
+ *   zk_frame_content_sizes, zk_read_ranges (host pointers)                          refused   served    refused
+ *   zk_decode_frames, zk_decode_frames_prefix, zk_decode_shard (host pipeline)      refused   refused   refused    (it rotates through both contexts)
+ *   zk_decoder_decompress[_with_prefix], zk_decoder_time_seeks: a read that needs   refused   refused   refused    (as ZK_ERR_IO "invalid argument", like every
+ *     a submission                                                                                                  engine failure through a handle; offset, limits,
+ *                                                                                                                   cache, read-ahead and counters stay)
+ *     ... a read the handle's cache serves, or the part of one that it serves        served    served    served
+ *     zk_decoder_set_* / _seek / _reset / the getters (the handle's own state)      served    served    served
+ *   zk_engine_set_dictionary                                                        refused   refused   refused    (a batch decodes against the dictionary it was
+ *                                                                                                                   submitted with)
+ *   zk_gather_seekable                                                              refused   refused   refused    (a collective waits for its peers)
+ *   zk_encode_frames[_prefix][_dev], zk_raw_encoder_*, zk_encoder_*                 served    served    served     (scratch of their own)
+ *   zk_xxh64_frames[_dev]                                                           served    served    served
+ *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
+ *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
+ *   zk_engine_checksums_followed / _entropy_fused / _ranges_frames_decoded /        served    served    served     ("the last finished decode" is the batch waited for
+ *     _kernel_times / _kernel_name / _last_hip_error / _device_name                                                 last, or a synchronous call after it)
+ *   zk_engine_destroy                                                               served    served    served     (completes the batches first; their buffers hold the
+ *                                                                                                                   results, their return codes are lost)
+ * Functions that take no engine and no handle opened on one (zk_dict_*, zk_seek_table_*, zk_serializer_*, zk_host_alloc / _free,
+ * zk_compress_bound, zk_shard_range, zk_set_collective_library) do not depend on any of this. */
 int zk_decode_submit_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off,
                          const void *d_d_off, uint32_t first, uint32_t count, void *d_dst, uint64_t dst_cap,
                          int verify, void *d_frame_status, int *slot_out);

@@ -192,6 +192,12 @@ size_t Decoder::decompress_with_prefix(uint8_t *buf, size_t len, const uint8_t *
             offset_ += n; progress += n;                                      // decode.rs:263-266
             continue;
         }
+        // from here on the read needs a submission, which the engine refuses while a batch of zk_decode_submit_dev is outstanding: asked
+        // first, so that the cache, the staged prefix and the counters stay as they are.  What the cache could serve is delivered
+        if (zk_batch_outstanding(engine_)) {
+            if (progress) return progress;
+            throw Error::from_engine_code(ZK_ERR_ARGUMENT, "");
+        }
         const uint64_t want = std::min<uint64_t>(offset_limit_, offset_ + (len - progress));
         const uint32_t first = seek_table_.frame_index_decomp(offset_);
         // whole frames inside the request go straight into the caller's buffer (no cache, no second copy): the engine

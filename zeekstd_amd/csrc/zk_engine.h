@@ -140,6 +140,9 @@ int zk_dec_fork(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st);     // the 
 int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, const zk_dec_args &a, const ZkSegScratch *sgs, const ZkDecShape &shape,
                           uint64_t nseq, uint64_t *prog, const uint32_t *rep_init);
 // does this call decode against the engine's dictionary?  (an explicit prefix overrides it, as ZSTD_DCtx_refPrefix does)
+// is a batch of zk_decode_submit_dev outstanding?  What an entry point refuses for (the table above zk_decode_submit_dev, zeekstd_amd.h) it refuses
+// with this, before it reserves, uploads or waits for anything
+inline bool zk_batch_outstanding(const zk_engine *e) { return e->slot_busy[0] || e->slot_busy[1]; }
 inline bool zk_dict_applies(const zk_engine *e, const void *d_prefix) { return e->dict.on && !d_prefix; }
 namespace zeekstd { class SeekTable; }
 struct zk_seek_table;

@@ -555,6 +555,7 @@ extern "C" int zk_frame_content_sizes(zk_engine *e, const uint8_t *comp, uint64_
     if (count == 0) return 0;
     const uint64_t lo = c_off[first], hi = c_off[first + count];
     if (hi < lo || hi > comp_size) return -(int)ZK_E_SRC_SIZE_WRONG;
+    if (e->slot_busy[0]) return ZK_ERR_ARGUMENT;            // refused before the staging: its uploads ride on context 0's queue, behind the batch
     ZK_HIP(hipSetDevice(e->device));
     int rc;
     std::vector<uint64_t> rel(count + 1);

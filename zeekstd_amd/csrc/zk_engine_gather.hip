@@ -84,6 +84,7 @@ extern "C" int zk_gather_seekable(zk_engine *e, void *nccl_comm, int rank, int w
     if (table_out) *table_out = nullptr;
     if (!e || !nccl_comm || world < 1 || rank < 0 || rank >= world || root < 0 || root >= world || (payload_bytes && !d_payload) ||
         (n_frames && (!c_sizes || !d_sizes))) return ZK_ERR_ARGUMENT;
+    if (zk_batch_outstanding(e)) return ZK_ERR_ARGUMENT;    // a collective waits for its peers: not behind, nor beside, a submitted batch (zk_decode_wait first)
     const Rccl R = rccl();
     if (!R.ok) { e->last_err = "RCCL (librccl.so.1) could not be loaded"; return ZK_ERR_HIP; }
     ZK_HIP(hipSetDevice(e->device));

@@ -522,7 +522,7 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
     if (n_ok) *n_ok = 0;
     if (!e || (count && (!c_off || !d_off || (!src.mem && !src.read)))) return ZK_ERR_ARGUMENT;
     if (count == 0) return 0;
-    if (e->slot_busy[0] || e->slot_busy[1]) return ZK_ERR_ARGUMENT;     // submitted batches own the decode contexts: zk_decode_wait first
+    if (zk_batch_outstanding(e)) return ZK_ERR_ARGUMENT;                // submitted batches own the decode contexts: zk_decode_wait first
     ZK_HIP(hipSetDevice(e->device));
     const uint64_t c_lo = c_off[first], d_lo = d_off[first], d_hi = d_off[first + count];
     // the offset arrays are the caller's: every entry is checked, not only the ends (prefix sums of a SeekTable pass trivially)
@@ -705,6 +705,7 @@ extern "C" int zk_decode_frames_prefix(zk_engine *e, const uint8_t *comp, uint64
     if (!e || (count && (!comp || !c_off || !d_off))) return ZK_ERR_ARGUMENT;
     if (count == 0) return 0;
     for (uint32_t i = 0; i <= count; i++) if (c_off[first + i] > comp_size) return ZK_ERR_ARGUMENT;
+    if (zk_batch_outstanding(e)) return ZK_ERR_ARGUMENT;    // (zk_host_decode's refusal, in front of the prefix's upload)
     const void *d_prefix = nullptr;
     if (!prefix) prefix_len = 0;
     // the prefix is uploaded on every call: nothing is cached by address (a caller may decode against base A, then against

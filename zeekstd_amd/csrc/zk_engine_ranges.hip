@@ -44,9 +44,9 @@ extern "C" int zk_read_ranges_dev(zk_engine *e, const void *d_comp, uint64_t com
                                   int verify, void *d_range_status, void *stream)
 {
     if (!e || !d_d_off || (count && (!d_offs || !d_lens)) || (n_frames && (!d_comp || !d_c_off))) return ZK_ERR_ARGUMENT;
+    if (count && e->slot_busy[0]) return ZK_ERR_ARGUMENT;   // a submitted batch still owns context 0: zk_decode_wait first (nothing touched, the counter included)
     e->ranges_frames = 0;
     if (count == 0) return 0;
-    if (e->slot_busy[0]) return ZK_ERR_ARGUMENT;            // a submitted batch still owns context 0: zk_decode_wait first
     ZK_HIP(hipSetDevice(e->device));
     zk_engine::DecCtx &x = e->dctx[0];
     hipStream_t st = zk_dec_stream(e, x, stream);
@@ -175,6 +175,7 @@ extern "C" int zk_read_ranges(zk_engine *e, const uint8_t *comp, uint64_t comp_s
         if (rfirst[i] != ~0u) h_off[i] = new_start[rfirst[i]] + (offs[i] - d_off[rfirst[i]]);
         out_bytes += h_len[i];
     }
+    if (e->slot_busy[0]) return ZK_ERR_ARGUMENT;            // refused before the staging: its uploads ride on context 0's queue, behind the batch
     ZK_HIP(hipSetDevice(e->device));
     hipStream_t st = e->stream;
     int rc;
