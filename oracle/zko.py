@@ -211,3 +211,35 @@ def enc_match_debug(src: bytes, level: int = 1, prefix: bytes = None):
         out.append((seqs[s0:s0 + int(nseq[b])].copy(), lits[l0:l0 + int(nlit[b])].tobytes()))
         s0 += int(nseq[b]); l0 += int(nlit[b])
     return out
+
+
+def enc_far_debug(src: bytes, level: int, dense: bool = True):
+    """The twin's far history of ONE frame without a prefix (zko_enc_far_debug): -> (sampled table as a uint32 array of 2^log entries,
+    dense candidates as a uint32 array [n, 3] of (d, l, bk) with zeros where a position has none, whether the level has dense history
+    here); (None, None, False) for a frame that gets no far history at this level."""
+    import numpy as np
+    src = bytes(src)
+    n = len(src)
+    l = lib()
+    l.zko_enc_far_debug.restype = C.c_int64
+    l.zko_enc_far_debug.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
+    table = np.zeros(1 << 23, np.uint32)
+    dlb = np.zeros((n, 3), np.uint32) if dense else None
+    on = C.c_int()
+    log = l.zko_enc_far_debug(src, n, level, table.ctypes.data, table.size, dlb.ctypes.data if dense else None, C.byref(on))
+    if log < 0:
+        return None, None, False
+    return table[:1 << log].copy(), dlb, bool(on.value)
+
+
+def enc_ldm_prefix_debug(prefix: bytes):
+    """The twin's sampled table over a prefix (zko_enc_ldm_prefix_debug): uint32 array of 2^log entries (position - u0 of the first sampled
+    occurrence per slot, 0xFFFFFFFF = empty); None for a prefix the matcher's ring holds."""
+    import numpy as np
+    prefix = bytes(prefix)
+    l = lib()
+    l.zko_enc_ldm_prefix_debug.restype = C.c_int64
+    l.zko_enc_ldm_prefix_debug.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    table = np.zeros(1 << 23, np.uint32)
+    log = l.zko_enc_ldm_prefix_debug(prefix, len(prefix), table.ctypes.data, table.size)
+    return None if log < 0 else table[:1 << log].copy()

@@ -460,7 +460,7 @@ static void ldm_build_frame(enc_state *st, const u8 *frame, size_t n)
  * copies of 16+ bytes; what libzstd's level 3 (cli/src/args.rs:192) gains over a 57 280-byte window on text are SHORT matches of rare words
  * whose last occurrence lies further back.  Per matcher segment g of the frame (ZKE_SEGMENT bytes, one GPU workgroup) two tables of
  * 2^dense_log slots over the 5-byte hash of EVERY position of the segment: first[g] = its smallest, last[g] = its largest position per slot
- * (order-free rules: the GPU builds them with LDS atomics, zk_k_enc_dense_build).  A position p of segment g looks ONE candidate up:
+ * (order-free rules: the GPU builds them with LDS atomics, zk_k_enc_dense_part / zk_k_enc_dense_cand).  A position p of segment g looks ONE candidate up:
  * first[g] if that lies more than ZKE_WINDOW bytes behind p (nearer ones are the ring's), else last[g - 1] under the same condition --
  * the nearest far copy the two tables know; older segments are not asked (measured on the 8d text at 2^17 slots: asking all of them
  * 2.7009, the one before 2.7088: a farther offset costs more bits than the match saves).  The candidate is taken if it is at least
@@ -773,6 +773,53 @@ i64 zko_enc_match_debug(const u8 *src, size_t n, int level, const u8 *prefix, si
     }
     free(st->ldm); free(st->dense); free(st); free(cat); free(sq);
     return nblk;
+}
+
+/* TEST SUPPORT: the far history of ONE frame without a prefix as the twin builds and asks it (ldm_build_frame, dense_build_frame,
+ * dense_lookup), for the tests that run the GPU's far-history kernels on the CPU (tests/sim/zk_enc_far_sim.cpp).
+ *   table[table_cap]  the sampled table, 2^log entries (0xFFFFFFFF = empty); the return value is log, -1 when the frame gets none at
+ *                     this level or table_cap is too small
+ *   dlb[3 * n]        (may be NULL) per position q the dense candidate as a plain triple, zeros where there is none:
+ *                       d   q - dense_lookup(q)
+ *                       l   bytes that frame[q..] and frame[q - d..] have in common, at most 16 and not past the frame's end
+ *                       bk  bytes in front of both that agree, at most 4 and not past the frame's first byte (the candidate's own position)
+ *                     an entry exists iff l >= ZKE_DENSE_MIN; positions are asked as find_sequences asks them (q + 8 <= n)
+ *   *dense_on         whether the level has dense history for this frame at all */
+i64 zko_enc_far_debug(const u8 *src, size_t n, int level, u32 *table, size_t table_cap, u32 *dlb, int *dense_on)
+{
+    if (dense_on) *dense_on = 0;
+    if (!ldm_wanted_in_frame(level, 0, n)) return -1;
+    enc_state *st = calloc(1, sizeof *st);
+    ldm_build_frame(st, src, n);
+    const u32 log = st->ldm_log;
+    if (((size_t)1 << log) > table_cap) { free(st->ldm); free(st); return -1; }
+    memcpy(table, st->ldm, sizeof(u32) << log);
+    if (dlb) memset(dlb, 0, 3 * n * sizeof(u32));
+    if (dense_wanted(level, 0, n)) {
+        if (dense_on) *dense_on = 1;
+        dense_build_frame(st, src, n, level);
+        for (u64 q = 0; dlb && q + 8 <= n; q++) {
+            const u64 c = dense_lookup(st, src + q, q);
+            if (c == ~0ull) continue;
+            const u32 d = (u32)(q - c);
+            u32 l = 0, bk = 0;
+            while (l < 16 && q + l < n && src[q + l] == src[c + l]) l++;
+            while (bk < 4 && bk < c && src[q - bk - 1] == src[c - bk - 1]) bk++;
+            if (l >= ZKE_DENSE_MIN) { dlb[3 * q] = d; dlb[3 * q + 1] = l; dlb[3 * q + 2] = bk; }
+        }
+    }
+    free(st->ldm); free(st->dense); free(st);
+    return log;
+}
+/* ... and the sampled table over a prefix (ldm_build): 2^log entries of position - u0; returns log, -1 when the prefix gets none */
+i64 zko_enc_ldm_prefix_debug(const u8 *prefix, size_t plen, u32 *table, size_t table_cap)
+{
+    enc_state *st = calloc(1, sizeof *st);
+    ldm_build(st, prefix, plen);
+    i64 log = -1;
+    if (st->ldm && ((size_t)1 << st->ldm_log) <= table_cap) { log = st->ldm_log; memcpy(table, st->ldm, sizeof(u32) << log); }
+    free(st->ldm); free(st);
+    return log;
 }
 
 static size_t nseq_header(u8 *d, u32 n) { if (n < 128) { d[0] = (u8)n; return 1; } if (n < 0x7F00) { d[0] = (u8)((n >> 8) + 128); d[1] = (u8)n; return 2; } d[0] = 255; d[1] = (u8)(n - 0x7F00); d[2] = (u8)((n - 0x7F00) >> 8); return 3; }

@@ -5,7 +5,10 @@
 //   wave collectives (__ballot, readlane, ds_bpermute, update_dpp row_shr:1, wave_barrier) -> the 64 lanes of a wave
 //                             deposit their value and park until the wave is complete; they must be called by all 64
 //                             lanes (wave-uniform control flow), as the kernels under test do
-//   atomicCAS on LDS       -> plain (fibers are cooperative)
+//   atomicCAS / atomicMin / atomicMax / atomicAdd -> plain (fibers are cooperative)
+//   gridDim, blockIdx.x / .y -> what emu_run_workgroup was told (defaults: a grid of one workgroup)
+// The scheduler visits the lanes in ascending order, or -- emu_set_lane_order(true) -- in descending order: a kernel whose result does
+// not depend on which lane reaches an atomic first gives the same output under both.
 // Lanes of a wave do NOT run in lock step here: code that relies on the in-order LDS pipeline of one wave needs a
 // __builtin_amdgcn_wave_barrier() (a scheduling fence on the device, a wave meeting point here).
 #pragma once
@@ -25,6 +28,8 @@ struct EmuWG {
     std::vector<EmuWave> waves;
     std::vector<char> stacks;
     uint32_t nthreads = 0, cur = 0, block = 0, live = 0;
+    uint32_t block_y = 0, grid_x = 1, grid_y = 1;
+    bool descending = false;
     uint32_t bar_count = 0; uint64_t bar_gen = 0;
     std::function<void()> body;
 };
@@ -32,7 +37,9 @@ static EmuWG g_emu;
 
 static inline void emu_yield() { swapcontext(&g_emu.lanes[g_emu.cur].ctx, &g_emu.sched); }
 static inline EmuDim emu_tidx() { return EmuDim{g_emu.lanes[g_emu.cur].tid, 0, 0}; }
-static inline EmuDim emu_bidx() { return EmuDim{g_emu.block, 0, 0}; }
+static inline EmuDim emu_bidx() { return EmuDim{g_emu.block, g_emu.block_y, 0}; }
+static inline EmuDim emu_gdim() { return EmuDim{g_emu.grid_x, g_emu.grid_y, 1}; }
+static inline void emu_set_lane_order(bool descending) { g_emu.descending = descending; }
 
 static inline void emu_barrier()
 {
@@ -85,6 +92,8 @@ static inline uint32_t emu_alignbyte(uint32_t hi, uint32_t lo, uint32_t s) { ret
 static inline uint32_t emu_atomic_cas(uint32_t *p, uint32_t cmp, uint32_t val) { const uint32_t old = *p; if (old == cmp) *p = val; return old; }
 
 static inline uint32_t emu_atomic_min(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v < old) *p = v; return old; }
+static inline uint32_t emu_atomic_max(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v > old) *p = v; return old; }
+static inline uint32_t emu_atomic_add(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old + v; return old; }
 
 static void emu_entry()
 {
@@ -95,12 +104,13 @@ static void emu_entry()
     swapcontext(&g.lanes[g.cur].ctx, &g.sched);
 }
 
-// run `body` (the kernel call) as workgroup `block` of `nthreads` lanes
-static void emu_run_workgroup(uint32_t nthreads, uint32_t block, std::function<void()> body)
+// run `body` (the kernel call) as workgroup (`block`, `block_y`) of `nthreads` lanes in a grid of grid_x x grid_y workgroups
+static void emu_run_workgroup(uint32_t nthreads, uint32_t block, std::function<void()> body, uint32_t grid_x = 1, uint32_t block_y = 0, uint32_t grid_y = 1)
 {
     EmuWG &g = g_emu;
     constexpr size_t STACK = 128 << 10;
     g.nthreads = nthreads; g.block = block; g.live = nthreads; g.body = body;
+    g.block_y = block_y; g.grid_x = grid_x; g.grid_y = grid_y;
     g.bar_count = 0;
     g.lanes.assign(nthreads, EmuLane());
     g.waves.assign((nthreads + 63) / 64, EmuWave());
@@ -115,7 +125,8 @@ static void emu_run_workgroup(uint32_t nthreads, uint32_t block, std::function<v
         makecontext(&l.ctx, emu_entry, 0);
     }
     while (g.live) {
-        for (uint32_t t = 0; t < nthreads; t++) {
+        for (uint32_t i = 0; i < nthreads; i++) {
+            const uint32_t t = g.descending ? nthreads - 1 - i : i;
             if (g.lanes[t].done) continue;
             g.cur = t;
             swapcontext(&g.sched, &g.lanes[t].ctx);
@@ -130,6 +141,7 @@ static void emu_run_workgroup(uint32_t nthreads, uint32_t block, std::function<v
 #define __launch_bounds__(...)
 #define threadIdx (emu_tidx())
 #define blockIdx (emu_bidx())
+#define gridDim (emu_gdim())
 #define __syncthreads() emu_barrier()
 #define ZKE_LDS_BARRIER() emu_barrier()
 #define __ballot(p) emu_ballot(p)
@@ -142,6 +154,8 @@ static void emu_run_workgroup(uint32_t nthreads, uint32_t block, std::function<v
 #define __builtin_amdgcn_readfirstlane(v) (v)          /* only used on values that are uniform across the wave */
 #define atomicCAS(p, c, v) emu_atomic_cas((p), (c), (v))
 #define atomicMin(p, v) emu_atomic_min((p), (v))
+#define atomicMax(p, v) emu_atomic_max((p), (v))
+#define atomicAdd(p, v) emu_atomic_add((p), (v))
 #define __ffs(x) __builtin_ffs(x)
 #define ZKE_FFBL(x) ((x) ? (uint32_t)__builtin_ctz(x) : 0xFFFFFFFFu)          /* v_ffbl_b32 */
 #define ZKE_FFBH(x) ((x) ? (uint32_t)__builtin_clz(x) : 0xFFFFFFFFu)          /* v_ffbh_u32 */

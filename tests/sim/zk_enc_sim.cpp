@@ -35,12 +35,14 @@ extern "C" int zk_enc_sim_match(const uint8_t *src, uint64_t n, uint32_t frame_s
         }
         msrc = stage.data();
     }
-    // long-distance table over the prefix (the engine builds it with zk_k_enc_ldm_build; here sequentially, same rule)
+    // long-distance table over the prefix (the engine builds it with zk_k_enc_ldm_build; here sequentially, same rule -- the kernel itself is
+    // held to that rule by tests/test_sim_enc_far.py::test_sampled_table_over_a_prefix_equals_twin)
     ZkEncLdm ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0};
     std::vector<uint32_t> table, dense;
     std::vector<uint8_t> pcopy;
     if (!prefix && zke_ldm_in_frame(level, 0, frame_size < n ? frame_size : n)) {
-        // in-frame far history: one table per frame over its own bytes (the engine: zk_k_enc_ldm_build_frames; here sequentially, same rule)
+        // in-frame far history: one table per frame over its own bytes (the engine: zk_k_enc_ldm_build_frames; here sequentially, same rule --
+        // the kernel itself is held to it by tests/test_sim_enc_far.py::test_sampled_tables_per_frame_equal_twin)
         ldm.inframe = 1; ldm.frame_size = frame_size; ldm.n_total = n; ldm.log = zke_ldm_log(frame_size < n ? frame_size : n);
         table.assign((size_t)pl.nf << ldm.log, ZKE_LDM_NONE);
         for (uint32_t f = 0; f < pl.nf; f++) {
@@ -57,7 +59,8 @@ extern "C" int zk_enc_sim_match(const uint8_t *src, uint64_t n, uint32_t frame_s
         ldm.table = table.data();
         if (zke_dense_in_frame(level, 0, frame_size < n ? frame_size : n)) {
             // dense far history: every position's far candidate out of the first / last occurrence per slot and segment (the engine:
-            // zk_k_enc_dense_cand; here sequentially, same rule)
+            // zk_k_enc_dense_cand; here sequentially, same rule -- the kernels themselves are held to it by
+            // tests/test_sim_enc_far.py::test_dense_candidates_equal_twin)
             ldm.dlog = zke_dense_log(level);
             dense.assign((size_t)n + ZKE_DENSE_SLACK, 0);
             const size_t slots = (size_t)1 << ldm.dlog;
