@@ -203,7 +203,7 @@ int zk_decode_frames_prefix(zk_engine *e, const uint8_t *comp, uint64_t comp_siz
  * zk_engine_set_dictionary uploads the dictionary once (the engine keeps its own device copy: the zk_dict may be freed right away);
  * NULL = none.  ZK_ERR_ARGUMENT while a submitted batch is outstanding (zk_decode_wait first).  With a dictionary set, every frame of
  * zk_decode_frames[_dev], zk_decode_frame_list_dev, zk_decode_submit_dev, zk_read_ranges[_dev], zk_frame_content_sizes[_dev],
- * zk_decode_shard and of the zk_decoder_* handles opened on the engine is decoded as libzstd decodes it after loadDictionary:
+ * zk_refine_entries[_dev], zk_decode_shard and of the zk_decoder_* handles opened on the engine is decoded as libzstd decodes it after loadDictionary:
  *   - a Dictionary_ID field that is absent, 0 or the dictionary's is accepted, any other value is -32 for that frame alone;
  *   - the dictionary's content lies right before the frame's first byte (offsets are bounded by availability, as with a prefix) and
  *     the repeat-offset history starts from the dictionary's three offsets;
@@ -231,6 +231,37 @@ int zk_frame_content_sizes(zk_engine *e, const uint8_t *comp, uint64_t comp_size
 int zk_frame_content_sizes_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off, uint32_t first, uint32_t count,
                                void *d_sizes, void *d_frame_status, void *stream);
 
+/* A seek table refined to ONE ENTRY PER FRAME, on the device.  An entry of a seek table may be any chain of Zstandard frames and skippable
+ * frames (seekable_format.md:41: an archive consists of "Zstandard compressed frames and skippable frames"; the reference seeks to the
+ * entry's first byte and libzstd's streaming decoder walks through whatever frames follow, lib/src/decode.rs:206-267), while every decode
+ * call here takes entries of exactly one frame.  The refined table is an ordinary seek table of the same bytes -- same totals, same entry
+ * boundaries, finer entries -- that every decode call, zk_read_ranges* and the handles serve; a seek under it decodes less.
+ *   c_off     n_entries + 1 prefix sums of compressed sizes
+ *   d_off     the same for decompressed sizes, or NULL = nobody knows them (a plain multi-frame .zst: n_entries = 1, c_off = {0, size})
+ *   c_out, d_out   out_cap + 1 prefix sums each (uint64); entry_of (optional, uint32, out_cap): the input entry refined entry j came from
+ *   entry_status   n_entries (int32): 0 or -(ZSTD_ErrorCode)
+ * - A good entry of k frames becomes k refined entries in order, skippable frames among them with size 0; each holds exactly one frame and
+ *   its decompressed size is what its blocks regenerate (obtained as zk_frame_content_sizes_dev obtains it, and held against
+ *   Frame_Content_Size where the frame carries one).  A dictionary set on the engine applies as it does there.
+ * - With d_off, the sizes of an entry's frames must sum to the entry's size (-20 otherwise) and d_out continues d_off: d_out[0] = d_off[0],
+ *   every entry boundary of d_off is one of d_out.  With d_off == NULL, d_out starts at 0.
+ * - A bad entry stays ONE refined entry: its own compressed range, its size from d_off (0 without one) and its code in entry_status, so the
+ *   refined table is always a total table of the archive and decoding it reports that entry as it is reported today.  The code is that of
+ *   the first frame of the entry that fails, as zk_decode_frames* and zk_frame_content_sizes* report a frame; -72 (srcSize_wrong: the entry's size does
+ *   not match its frames) where fewer than 4 bytes are left behind a complete frame or the bytes left begin with neither magic; -14 where a
+ *   frame decodes to more than SEEKABLE_MAX_FRAME_SIZE.
+ * - *n_out (the refined entries) is always set and entry_status always written.  If *n_out > out_cap nothing else is written and -70 comes
+ *   back: out_cap = 0 with NULL c_out / d_out / entry_of asks for the size.  n_entries == 0: *n_out = 0, nothing written, 0.
+ * Returns 0, or the status of the first failing entry with the arrays still valid; engine errors as everywhere.  It runs on decode context 0
+ * (the table above zk_decode_submit_dev); per-kernel profiling is off inside it.  The work is parallel over ENTRIES: a stream without a table
+ * is one serial chain (frame i + 1 begins where frame i's last block ends) walked by one lane.
+ * _dev: device pointers, c_off relative to d_comp, which must be readable ZK_COMP_PADDING bytes past comp_size.  zk_refine_entries: host
+ * pointers; comp[c_off[0], c_off[n_entries]) is uploaded. */
+int zk_refine_entries_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off, uint32_t n_entries,
+                          void *d_c_out, void *d_d_out, void *d_entry_of, uint32_t out_cap, uint32_t *n_out, void *d_entry_status, void *stream);
+int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off, const uint64_t *d_off, uint32_t n_entries,
+                      uint64_t *c_out, uint64_t *d_out, uint32_t *entry_of, uint32_t out_cap, uint32_t *n_out, int32_t *entry_status);
+
 /* Two batches in flight.  zk_decode_submit_dev enqueues exactly what zk_decode_frames_dev runs, on one of the
  * engine's two decode contexts (own HIP queues and scratch), and returns while the kernels are still running;
  * *slot_out names the context.  zk_decode_wait(slot) blocks until that batch is complete and returns its status (0,
@@ -257,6 +288,7 @@ int zk_frame_content_sizes_dev(zk_engine *e, const void *d_comp, uint64_t comp_s
  *   zk_decode_frames_dev, zk_decode_frames_prefix_dev, zk_decode_frame_list_dev     refused   served    refused    (they run on context 0,
  *   zk_frame_content_sizes_dev, zk_read_ranges_dev                                  refused   served    refused     also on the caller's stream)
  *   zk_frame_content_sizes, zk_read_ranges (host pointers)                          refused   served    refused
+ *   zk_refine_entries_dev, zk_refine_entries                                        refused   served    refused    (context 0; *n_out and the arrays stay)
  *   zk_decode_frames, zk_decode_frames_prefix, zk_decode_shard (host pipeline)      refused   refused   refused    (it rotates through both contexts)
  *   zk_decoder_decompress[_with_prefix], zk_decoder_time_seeks: a read that needs   refused   refused   refused    (as ZK_ERR_IO "invalid argument", like every
  *     a submission                                                                                                  engine failure through a handle; offset, limits,
@@ -411,6 +443,11 @@ uint64_t zk_seek_table_size_decomp(const zk_seek_table *t);                     
 int zk_seek_table_equal(const zk_seek_table *a, const zk_seek_table *b);                       /* PartialEq :266 */
 /* the n+1 prefix sums (what zk_decode_frames takes); returns n+1 */
 size_t zk_seek_table_entries(const zk_seek_table *t, uint64_t *c_off, uint64_t *d_off, size_t cap);
+/* engine-specific (zk_refine_entries above): table t of the compressed stream src[0, len) -- the frames only -- refined to one entry per frame.
+ * t == NULL: one entry over all of it, sizes unknown: the way to give a plain multi-frame .zst (pzstd output, `cat a.zst b.zst`) a seek
+ * table.  The result is built with log_frame, so its errors apply (:513-525).  On a bad entry its code comes back, *out stays NULL and
+ * zk_last_error_message says which error it was. */
+int zk_seek_table_refine(zk_engine *e, const uint8_t *src, size_t len, const zk_seek_table *t, zk_seek_table **out);
 /* ---- Serializer (seek_table.rs:937-1059): resumable at byte granularity, 0 == done */
 zk_serializer *zk_seek_table_serializer(const zk_seek_table *t, int format);                   /* into_format_serializer :907 */
 size_t zk_serializer_write_into(zk_serializer *s, uint8_t *buf, size_t len);                   /* :967-1005 */
@@ -425,6 +462,13 @@ typedef struct zk_decoder zk_decoder;
 #define ZK_DEC_HAS_LOWER_FRAME 4u
 #define ZK_DEC_HAS_UPPER_FRAME 8u
 #define ZK_DEC_NO_VERIFY 16u
+/* engine-specific: every zk_decoder_open_* refines the table it was given or parsed against the source before the first read
+ * (zk_refine_entries; the source is read in groups of whole entries of at most 256 MiB compressed, a larger entry alone), and
+ * zk_decoder_seek_table returns the refined table.  lower_frame / upper_frame index the table as given.  For archives whose entries hold several
+ * frames or skippable frames, which fail with -72 / -10 otherwise.  A bad entry does not fail the open: it stays as it is and fails
+ * when it is read.  The open itself runs zk_refine_entries: it fails (ZK_ERR_IO) while decode context 0 holds a submitted batch.  Without
+ * the flag nothing changes. */
+#define ZK_DEC_REFINE_ENTRIES 32u
 typedef struct zk_decode_opts {          /* DecodeOptions builder fields, decode.rs:13-114 */
     uint32_t flags;
     uint32_t lower_frame, upper_frame;   /* :73, :81 (upper is inclusive) */

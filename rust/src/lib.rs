@@ -111,6 +111,19 @@ impl SeekTable {
         assert_eq!(c_sizes.len(), d_sizes.len());
         check(unsafe { ffi::zk_seek_table_log_frames(self.0, c_sizes.len() as u32, c_sizes.as_ptr(), d_sizes.as_ptr()) })
     }
+    /// engine-specific (`zk_seek_table_refine`): this table of the compressed stream `src` (the frames only) refined to one entry per
+    /// frame; its entries may be chains of Zstandard frames and skippable frames.  The first bad entry's code is the error.
+    pub fn refined(&self, engine: &Engine, src: &[u8]) -> Result<Self> {
+        let mut t = core::ptr::null_mut();
+        check(unsafe { ffi::zk_seek_table_refine(engine.as_ptr(), src.as_ptr(), src.len(), self.0, &mut t) })?;
+        Ok(SeekTable(t))
+    }
+    /// ... with no table at all: a seek table for a plain multi-frame stream (one entry over all of `src`, sizes unknown)
+    pub fn refined_plain(engine: &Engine, src: &[u8]) -> Result<Self> {
+        let mut t = core::ptr::null_mut();
+        check(unsafe { ffi::zk_seek_table_refine(engine.as_ptr(), src.as_ptr(), src.len(), core::ptr::null(), &mut t) })?;
+        Ok(SeekTable(t))
+    }
     pub fn num_frames(&self) -> u32 { unsafe { ffi::zk_seek_table_num_frames(self.0) } }                              // :540
     pub fn frame_index_comp(&self, offset: u64) -> u32 { unsafe { ffi::zk_seek_table_frame_index_comp(self.0, offset) } }     // :560
     pub fn frame_index_decomp(&self, offset: u64) -> u32 { unsafe { ffi::zk_seek_table_frame_index_decomp(self.0, offset) } } // :579
@@ -292,10 +305,10 @@ unsafe extern "C" fn integrity_cb<S: Seekable>(user: *mut c_void, format: c_int,
 /// decode.rs:13-114
 pub struct DecodeOptions<'a, S: Seekable> {
     src: S, engine: Option<&'a Engine>, seek_table: Option<SeekTable>,
-    lower_frame: Option<u32>, upper_frame: Option<u32>, offset: Option<u64>, offset_limit: Option<u64>,
+    lower_frame: Option<u32>, upper_frame: Option<u32>, offset: Option<u64>, offset_limit: Option<u64>, refine: bool,
 }
 impl<'a, S: Seekable> DecodeOptions<'a, S> {
-    pub fn new(src: S) -> Self { DecodeOptions { src, engine: None, seek_table: None, lower_frame: None, upper_frame: None, offset: None, offset_limit: None } }   // :30
+    pub fn new(src: S) -> Self { DecodeOptions { src, engine: None, seek_table: None, lower_frame: None, upper_frame: None, offset: None, offset_limit: None, refine: false } }   // :30
     pub fn try_new(src: S) -> Option<Self> { Some(Self::new(src)) }                                         // :37 (nothing to create yet: see EncodeOptions::try_new)
     pub fn engine(mut self, e: &'a Engine) -> Self { self.engine = Some(e); self }                          // with_dctx :43
     pub fn seek_table(mut self, t: SeekTable) -> Self { self.seek_table = Some(t); self }                   // :65
@@ -303,6 +316,8 @@ impl<'a, S: Seekable> DecodeOptions<'a, S> {
     pub fn upper_frame(mut self, i: u32) -> Self { self.upper_frame = Some(i); self }                       // :81
     pub fn offset(mut self, o: u64) -> Self { self.offset = Some(o); self }                                 // :90
     pub fn offset_limit(mut self, l: u64) -> Self { self.offset_limit = Some(l); self }                     // :99
+    /// engine-specific (`ZK_DEC_REFINE_ENTRIES`): the table is refined to one entry per frame against the source when the decoder opens
+    pub fn refine_entries(mut self, on: bool) -> Self { self.refine = on; self }
     pub fn into_decoder(self) -> Result<Decoder<'a, S>> { Decoder::with_opts(self) }                        // :111
 }
 
@@ -317,6 +332,7 @@ impl<'a, S: Seekable> Decoder<'a, S> {
         if o.offset_limit.is_some() { flags |= ffi::ZK_DEC_HAS_OFFSET_LIMIT; }
         if o.lower_frame.is_some() { flags |= ffi::ZK_DEC_HAS_LOWER_FRAME; }
         if o.upper_frame.is_some() { flags |= ffi::ZK_DEC_HAS_UPPER_FRAME; }
+        if o.refine { flags |= ffi::ZK_DEC_REFINE_ENTRIES; }
         let opts = ffi::ZkDecodeOpts {
             flags, lower_frame: o.lower_frame.unwrap_or(0), upper_frame: o.upper_frame.unwrap_or(0), offset: o.offset.unwrap_or(0),
             offset_limit: o.offset_limit.unwrap_or(0), seek_table: o.seek_table.as_ref().map_or(core::ptr::null(), |t| t.0 as *const _), batch_bytes: 0,

@@ -67,6 +67,8 @@ _sig = {
     "zk_xxh64_frames_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     "zk_frame_content_sizes": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "zk_frame_content_sizes_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "zk_refine_entries_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P, _P]),
+    "zk_refine_entries": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
     "zk_dict_create": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "zk_dict_free": (None, [_P]),
     "zk_dict_id": (C.c_uint32, [_P]),

@@ -69,6 +69,7 @@ for _n, _r, _a in [
     ("zk_seek_table_size_comp", C.c_uint64, [_P]), ("zk_seek_table_size_decomp", C.c_uint64, [_P]),
     ("zk_seek_table_equal", C.c_int, [_P, _P]),
     ("zk_seek_table_entries", C.c_size_t, [_P, _P, _P, C.c_size_t]),
+    ("zk_seek_table_refine", C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(_P)]),
     ("zk_seek_table_serializer", _P, [_P, C.c_int]),
     ("zk_serializer_write_into", C.c_size_t, [_P, _P, C.c_size_t]),
     ("zk_serializer_reset", None, [_P]), ("zk_serializer_encoded_len", C.c_size_t, [_P]), ("zk_serializer_free", None, [_P]),
@@ -163,6 +164,22 @@ class SeekTable:                       # seek_table.rs:243-935
 
     def clone(self):
         return SeekTable(lib.zk_seek_table_clone(self._h))
+
+    @staticmethod
+    def _refine(engine, data, table):
+        data = bytes(data)
+        h = _P()
+        _chk(lib.zk_seek_table_refine(engine._h, data, len(data), table._h if table is not None else None, C.byref(h)))
+        return SeekTable(h)
+
+    class _Refined:
+        """table.refined(engine, data) / SeekTable.refined(engine, data): zk_seek_table_refine -- the table of the compressed stream `data`
+        (the frames only) refined to one entry per frame; entries may be chains of Zstandard and skippable frames.  On the class, with no
+        table: one entry over all of `data`, sizes unknown -- a seek table for a plain multi-frame stream.  Error with the first bad
+        entry's code."""
+        def __get__(self, obj, cls):
+            return lambda engine, data: cls._refine(engine, data, obj)
+    refined = _Refined()
 
     def log_frame(self, c_size: int, d_size: int):
         _chk(lib.zk_seek_table_log_frame(self._h, c_size, d_size))
@@ -269,6 +286,11 @@ class DecodeOptions:                   # decode.rs:13-114
     def verify_checksums(self, v: bool):
         if not v:
             self._o.flags |= 16
+        return self
+
+    def refine_entries(self, on: bool = True):
+        """ZK_DEC_REFINE_ENTRIES: the table is refined to one entry per frame against the source when the decoder opens"""
+        self._o.flags = (self._o.flags | 32) if on else (self._o.flags & ~32)
         return self
 
     def into_decoder(self):

@@ -108,6 +108,20 @@ size_t zk_seek_table_entries(const zk_seek_table *t, uint64_t *c_off, uint64_t *
     return e.size();
 }
 
+int zk_seek_table_refine(zk_engine *e, const uint8_t *src, size_t len, const zk_seek_table *t, zk_seek_table **out)
+{
+    if (!out) return ZK_ERR_ARGUMENT;
+    *out = nullptr;
+    if (!e || (len && !src)) return ZK_ERR_ARGUMENT;
+    return guard([&] {
+        BytesWrapper w(src, len);
+        int bad = 0;
+        SeekTable r = refine_seek_table(e, w, t ? &t->t : nullptr, len, &bad);
+        if (bad) throw Error::zstd((uint32_t)(-bad));        // (Display: ZSTD_getErrorName of the first bad entry's code)
+        *out = new zk_seek_table{std::move(r)};
+    });
+}
+
 zk_serializer *zk_seek_table_serializer(const zk_seek_table *t, int format)
 {
     return new (std::nothrow) zk_serializer{t->t.into_format_serializer(format == ZK_FORMAT_HEAD ? Format::Head : Format::Foot)};
@@ -129,6 +143,7 @@ static DecodeOptions make_opts(std::shared_ptr<Seekable> src, zk_engine *e, cons
         if (o->flags & ZK_DEC_HAS_OFFSET) opts.offset(o->offset);
         if (o->flags & ZK_DEC_HAS_OFFSET_LIMIT) opts.offset_limit(o->offset_limit);
         if (o->flags & ZK_DEC_NO_VERIFY) opts.verify_checksums(false);
+        if (o->flags & ZK_DEC_REFINE_ENTRIES) opts.refine_entries(true);
         if (o->batch_bytes) opts.batch_bytes(o->batch_bytes);
     }
     return opts;

@@ -37,6 +37,11 @@ Decoder::Decoder(DecodeOptions &&opts)                                        //
         if (rc != 0) throw Error::from_engine_code(rc);
         owns_engine_ = true;
     }
+    if (opts.refine_) {
+        // same bytes, same totals, same entry boundaries: offset and limit above stay what they are
+        try { int bad = 0; seek_table_ = refine_seek_table(engine_, *src_, &seek_table_, 0, &bad); }
+        catch (...) { if (owns_engine_) zk_engine_destroy(engine_); engine_ = nullptr; throw; }
+    }
 }
 
 Decoder::~Decoder()
@@ -75,6 +80,63 @@ static size_t seekable_pull(void *user, uint64_t off, uint8_t *dst, size_t n)
         sp->src->set_offset(OffsetFrom::Start(off));
         return sp->src->read(dst, n);
     } catch (...) { sp->error = std::current_exception(); return 0; }
+}
+
+SeekTable refine_seek_table(zk_engine *e, Seekable &src, const SeekTable *t, uint64_t plain_len, int *first_bad)
+{
+    *first_bad = 0;
+    std::vector<uint64_t> c, d;
+    if (t) for (const auto &en : t->entries()) { c.push_back(en.c_offset); d.push_back(en.d_offset); }
+    else c = {0, plain_len};
+    const uint32_t n = (uint32_t)(c.size() - 1);
+    size_t mem_len = 0;
+    const uint8_t *mem = src.contiguous(&mem_len);
+    if (mem && c[n] > mem_len) throw Error::zstd(72 /* srcSize_wrong */);
+    SeekablePull pull{&src, nullptr};
+    SeekTable out;
+    std::vector<uint8_t> stage;
+    std::vector<uint64_t> rel, co, dd;
+    std::vector<int32_t> st;
+    for (uint32_t f = 0; f < n;) {
+        uint32_t g = f + 1;
+        while (g < n && c[g + 1] - c[f] <= REFINE_GROUP_BYTES) g++;
+        const uint32_t cnt = g - f;
+        const uint64_t bytes = c[g] - c[f];
+        const uint8_t *comp = mem;
+        uint64_t base = 0, comp_size = mem_len;
+        if (!mem) {                                          // (as the host pipeline pulls: set_offset + read until the group is there)
+            stage.resize((size_t)bytes + 8);
+            uint64_t got = 0;
+            while (got < bytes) {
+                const size_t k = seekable_pull(&pull, c[f] + got, stage.data() + got, (size_t)(bytes - got));
+                if (pull.error) std::rethrow_exception(pull.error);
+                if (!k) throw Error::zstd(72 /* srcSize_wrong: the source ends inside its entries */);
+                got += k;
+            }
+            comp = stage.data(); base = c[f]; comp_size = bytes;
+        }
+        rel.resize(cnt + 1);
+        for (uint32_t i = 0; i <= cnt; i++) rel[i] = c[f + i] - base;
+        st.assign(cnt, 0);
+        uint32_t cap = cnt + 4096, m = 0;
+        int rc;
+        for (;;) {
+            co.assign((size_t)cap + 1, 0); dd.assign((size_t)cap + 1, 0);
+            rc = zk_refine_entries(e, comp, comp_size, rel.data(), t ? d.data() + f : nullptr, cnt, co.data(), dd.data(), nullptr, cap, &m, st.data());
+            if (rc <= -1000) throw Error::from_engine_code(rc, zk_engine_last_hip_error(e));
+            if (m > cap) { cap = m; continue; }              // (-70: now the size is known)
+            if (m == 0) throw Error::from_engine_code(rc ? rc : -1);
+            break;
+        }
+        if (!*first_bad) for (uint32_t i = 0; i < cnt; i++) if (st[i]) { *first_bad = st[i]; break; }
+        for (uint32_t j = 0; j < m; j++) {
+            const uint64_t cs = co[j + 1] - co[j], ds = dd[j + 1] - dd[j];
+            if (cs > 0xFFFFFFFFull || ds > 0xFFFFFFFFull) throw Error::number_conversion_failed("a refined entry does not fit a seek-table entry");
+            out.log_frame((uint32_t)cs, (uint32_t)ds);
+        }
+        f = g;
+    }
+    return out;
 }
 
 // A seek table is untrusted input: entries that cannot describe a zstd frame are refused before anything is sized from

@@ -193,6 +193,9 @@ public:
     // engine-specific knobs (no reference counterpart): how much to decode per GPU submission
     DecodeOptions &batch_bytes(uint64_t b) { batch_bytes_ = b; return *this; }
     DecodeOptions &verify_checksums(bool v) { verify_ = v; return *this; }
+    // ... the table (given or parsed) is refined to one entry per frame against the source before the first read (refine_seek_table):
+    // for archives whose entries hold several frames or skippable frames.  A bad entry stays as it is and fails when it is read
+    DecodeOptions &refine_entries(bool r) { refine_ = r; return *this; }
     Decoder into_decoder();                                                          // :111
 
 private:
@@ -203,8 +206,14 @@ private:
     std::optional<uint32_t> lower_frame_, upper_frame_;
     std::optional<uint64_t> offset_, offset_limit_;
     uint64_t batch_bytes_ = 64ull << 20;
-    bool verify_ = true;
+    bool verify_ = true, refine_ = false;
 };
+
+// engine-specific (zk_refine_entries, include/zeekstd_amd.h): the table of the frames in `src` refined to one entry per frame, built with
+// log_frame (its errors apply).  t == nullptr: one entry over src[0, plain_len), sizes unknown.  The source is read in groups of whole
+// entries of at most 256 MiB compressed (a larger entry goes alone).  A bad entry stays one entry; *first_bad: 0, or the code of the first
+constexpr uint64_t REFINE_GROUP_BYTES = 256ull << 20;
+SeekTable refine_seek_table(zk_engine *e, Seekable &src, const SeekTable *t, uint64_t plain_len, int *first_bad);
 
 class Decoder {                                                                      // decode.rs:117-466
 public:

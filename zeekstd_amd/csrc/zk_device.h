@@ -689,7 +689,16 @@ ZK_HD void zk_walk_frame(const uint8_t *comp, uint64_t c_begin, uint64_t c_end, 
     uint64_t csz = c_end - c_begin;
     const uint8_t *f = comp + c_begin;
     if (csz < 6) { fi.status = ZK_E_SRC_SIZE_WRONG; return; }
-    if (zk_rd32(f) != 0xFD2FB528u) { fi.status = ZK_E_PREFIX_UNKNOWN; return; }
+    const uint32_t magic = zk_rd32(f);
+    if (magic != 0xFD2FB528u) {
+        // a skippable frame (RFC 8878 3.1.2: magic 0x184D2A5?, Frame_Size, that many bytes) is an entry of its own that decodes to nothing
+        // (seekable_format.md: Decompressed_Size 0 "for skippable or otherwise empty frames"): status OK and NO block -- the one frame that has none
+        if ((magic & 0xFFFFFFF0u) != 0x184D2A50u) { fi.status = ZK_E_PREFIX_UNKNOWN; return; }
+        if (csz < 8 || 8ull + zk_rd32(f + 4) != csz) { fi.status = ZK_E_SRC_SIZE_WRONG; return; }
+        if (d_size != 0 && d_size != ZK_SIZE_UNKNOWN) { fi.status = ZK_E_CORRUPTION; return; }
+        fi.fcs = 0;
+        return;
+    }
     uint32_t fhd = f[4];
     uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, cks = (fhd >> 2) & 1, did = fhd & 3;
     if (fhd & 0x08) { fi.status = ZK_E_FRAMEPARAM_UNSUPPORTED; return; }

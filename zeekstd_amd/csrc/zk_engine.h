@@ -38,6 +38,7 @@ struct zk_engine {
     int next_slot = 0;
     // staging for the host-pointer entry points
     zk_devbuf st_comp, st_off, st_dst, st_misc;
+    zk_devbuf rf_entries, rf_frames;        // zk_refine_entries_dev (zk_refine.hip): scratch per entry, per piece
     // staged device copy of a raw-content prefix.  The host-pointer Level-A calls upload it on EVERY call (no caching by
     // address: a caller may reuse one buffer for different bases).  A zeekstd::Decoder / Encoder, whose contract is the
     // reference's borrow ("the prefix stays unchanged while it is referenced", decode.rs:201), keeps its upload across its

@@ -166,7 +166,7 @@ extern "C" void zk_engine_destroy(zk_engine *e)
     zk_hostpipe_destroy(e);
     if (e->enc.pin) (void)hipHostFree(e->enc.pin);
     for (auto &c : e->dctx) if (c.st) (void)hipStreamSynchronize(c.st);
-    zk_devbuf *bufs[] = {&e->dict.buf, &e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc,
+    zk_devbuf *bufs[] = {&e->dict.buf, &e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc, &e->rf_entries, &e->rf_frames,
                          &e->enc.lists, &e->enc.seqs, &e->enc.lits, &e->enc.scratch, &e->enc.words, &e->enc.ftab, &e->enc.hist, &e->enc.seg, &e->enc.ldm, &e->enc.dense};
     for (zk_devbuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (e->h_words) (void)hipHostFree(e->h_words);

@@ -103,6 +103,40 @@ class Engine:
             self._raise(rc)
         return sizes[:count], st[:count]
 
+    def refine_entries(self, comp: bytes, c_off, d_off=None, raise_on_error=False):
+        """zk_refine_entries: the table (c_off, d_off) of `comp` refined to one entry per frame.  An entry may be any chain of Zstandard
+        and skippable frames; d_off=None: nobody knows the sizes (a plain multi-frame stream: c_off = [0, len(comp)]).
+        -> (c_off', d_off', entry_of, status): uint64 prefix sums of the refined table, the input entry each refined entry came from, and
+        per INPUT entry 0 or -ZSTD_ErrorCode (a bad entry stays one refined entry)."""
+        c = _u64(c_off)
+        d = _u64(d_off) if d_off is not None else None
+        n = len(c) - 1
+        src = np.frombuffer(bytes(comp) + b"\0" * 8, np.uint8)
+        st = np.zeros(max(n, 1), np.int32)
+        n_out = C.c_uint32()
+        args = (self._h, src.ctypes.data, len(comp), c.ctypes.data, d.ctypes.data if d is not None else None, n)
+        rc = lib.zk_refine_entries(*args, None, None, None, 0, C.byref(n_out), st.ctypes.data)
+        if rc != -70 and rc != 0:
+            self._raise(rc)
+        m = n_out.value
+        co, do, eo = np.zeros(m + 1, np.uint64), np.zeros(m + 1, np.uint64), np.zeros(max(m, 1), np.uint32)
+        if m:
+            rc = lib.zk_refine_entries(*args, co.ctypes.data, do.ctypes.data, eo.ctypes.data, m, C.byref(n_out), st.ctypes.data)
+            if rc <= -1000 or (rc != 0 and raise_on_error):
+                self._raise(rc)
+        return co, do, eo[:m], st[:n]
+
+    def refine_entries_dev(self, d_comp, comp_size, d_c_off, d_d_off, n_entries, d_c_out, d_d_out, d_entry_of, out_cap, d_status, stream=None):
+        """zk_refine_entries_dev on device buffers (torch tensors or raw ints; d_d_off, d_c_out, d_d_out, d_entry_of may be None)
+        -> (return code, number of refined entries)"""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        n_out = C.c_uint32()
+        rc = lib.zk_refine_entries_dev(self._h, self._ptr(d_comp), comp_size, self._ptr(d_c_off), opt(d_d_off), n_entries,
+                                       opt(d_c_out), opt(d_d_out), opt(d_entry_of), out_cap, C.byref(n_out), self._ptr(d_status), stream)
+        if rc <= -1000 and rc != -2003:
+            self._raise(rc)
+        return rc, n_out.value
+
     def checksums_followed(self):
         """Frames of the last finished decode that zk_k_xxh64_follow verified beside the executor (zk_engine_checksums_followed)."""
         return int(lib.zk_engine_checksums_followed(self._h))
