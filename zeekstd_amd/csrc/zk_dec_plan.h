@@ -52,7 +52,7 @@ struct ZkDecShape {
 // 2048 frames of 2 MiB (profiles/r04_follow_by_batch_size.txt; ms one batch at a time | two in flight; behind = the better of
 // the two passes behind the executor):   16: 4.27 -> 3.50 | 2.19 -> 1.91     128: 5.20 -> 5.77 | 3.03 -> 3.07
 //                                       512: 6.48 -> 6.76 | 5.32 -> 5.13    2048: 16.7 -> 15.7 | 14.56 -> 14.49 (at four executor
-// workgroups per CU; five, the in-flight default, and a checksum wave do not fit a SIMD).  A few frames leave most CUs to the checksum
+// workgroups per CU; five, the in-flight default when this was measured, and a checksum wave do not fit a SIMD).  A few frames leave most CUs to the checksum
 // waves; a batch that fills the device alone trades 2.7 ms of an idle device for 1.7 ms of the executor; in between a frame IS a
 // workgroup and the slowest one -- the one that shares its SIMD -- ends the kernel.  Frames of less than 512 KiB are short chains.
 inline bool zk_follow_wanted(const ZkDecShape &s)
@@ -178,7 +178,9 @@ inline ZkEntropyPlan zk_entropy_plan(uint32_t nblocks, uint32_t n_own_tables, ui
 struct ZkExecPlan { int lanes, ring; uint32_t lds_pad; };     // lanes 128 / 256 / 512 / 1024; a ring of ring x lanes records; lds_pad: LDS asked for and not used
 // follow: the checksums run beside this executor (zk_k_xxh64_follow) and want registers left on every SIMD.  (The small path passes
 // nseq = 0 -- it does not read the totals back -- and follow = false although its checksums may run beside: kept as it was measured.)
-inline ZkExecPlan zk_exec_plan(uint32_t count, uint64_t nseq, uint64_t out_bytes, bool has_prefix, bool follow, const ZkKernelChoice &k)
+// beside: a batch of the engine was in flight on the other context when this one was enqueued (zk_dec_args::neighbour) and this batch took
+// zk_k_entropy_frame -- batches follow each other alike, so that kernel of the next batch is what shares the CUs with this executor.
+inline ZkExecPlan zk_exec_plan(uint32_t count, uint64_t nseq, uint64_t out_bytes, bool has_prefix, bool follow, const ZkKernelChoice &k, bool beside = false)
 {
     // ... what a frame's matches reach: dense sequence streams (fewer than 10 output bytes per sequence: libzstd from level 3 up, whose
     // window is the whole 2 MiB frame -- every far match a line from beyond the L2) run better with FEWER frames resident: 512-lane tiles
@@ -198,9 +200,14 @@ inline ZkExecPlan zk_exec_plan(uint32_t count, uint64_t nseq, uint64_t out_bytes
         // early; 4 T keep them whole (executor -8.5 % there, +2 % on sparser streams, hence the switch)
         if (lanes == 256 && (k.exec_ring ? k.exec_ring == 2 : (count >= 1024 && dense))) p.ring = 4;
     }
-    // 93 registers and 31 000 bytes of LDS: five 256-lane workgroups per CU.  Four of them leave 128 registers on every SIMD (room for
+    // 93 registers and 31 032 bytes of LDS: five 256-lane workgroups per CU.  Four of them leave 128 registers on every SIMD (room for
     // checksum waves, zk_k_xxh64_follow); a launch that asks for 2.5 KiB more LDS than the kernel uses gets four
-    const int resident = follow && !k.exec_resident ? 4 : k.exec_resident;
+    // (tests/test_entropy_budget.py pins the size both counts rest on).
+    // Four, too, beside another batch of long frames that takes zk_k_entropy_frame: the fifth executor workgroup of a CU costs the
+    // neighbour's entropy kernel more than it gives this one.  2 048 frames of 2 MiB, two batches in flight: the step 12.64-12.67 -> 12.25-12.34 ms;
+    // three per CU, and four beside the other entropy kernels, are slower (profiles/r09_entropy_resident.txt).  Measured on that shape only.
+    const bool long_frames = out_bytes >= (uint64_t)count * ZK_FOLLOW_MIN_FRAME_BYTES;
+    const int resident = k.exec_resident ? k.exec_resident : follow || (beside && long_frames) ? 4 : 0;
     if (p.lanes == 256 && resident == 4) p.lds_pad = 2560u;
     return p;
 }

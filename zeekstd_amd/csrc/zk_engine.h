@@ -111,6 +111,7 @@ struct zk_dec_args {
     void *d_dst; uint64_t dst_cap; int verify; void *d_frame_status;
     const void *d_prefix; uint64_t prefix_len;
     bool alone = false;                                 // nothing else of this engine is in flight (the synchronous entry points): zk_k_xxh64_follow
+    bool neighbour = false;                             // a batch of this engine is in flight on the other context as this one is enqueued: zk_exec_plan
     bool single_queue = false;                          // huf and fse on the context's main queue (the host pipeline overlaps whole chunks instead)
     bool mark_exec = false;                             // record the context's ev_exec behind the executor (output bytes final, checksums pending)
 };

@@ -302,7 +302,7 @@ int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, co
     const uint32_t x_first = a.out_off ? 0 : a.first;
     const uint64_t plen = a.d_prefix ? a.prefix_len : 0;
     if (sgs) { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec_seg(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, *sgs, zk_exec_seg_plan(a.count, sgs->max_segs, nseq, shape.out_bytes, shape.k), prog); }
-    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, (const uint8_t *)a.d_prefix, plen, zk_exec_plan(a.count, nseq, shape.out_bytes, plen != 0, shape.follow, shape.k), prog, rep_init); }
+    else { zk_kernel_timer t(e, ZK_K_EXEC, st); zk_launch_exec(st, comp, d_off, a.first, a.count, a.ids, a.out_off, blocks, bases, infos, seqs, lit, dst, (const uint8_t *)a.d_prefix, plen, zk_exec_plan(a.count, nseq, shape.out_bytes, plen != 0, shape.follow, shape.k, a.neighbour && c.fused), prog, rep_init); }
     if (a.mark_exec) ZK_HIP(hipEventRecord(c.ev_exec, st));
     if (prog) {
         // enqueued BEHIND the executor's launch: were the two queues ever served one after the other, the checksum waves would find
@@ -401,6 +401,7 @@ static int zk_decode_impl(zk_engine *e, const zk_dec_args &a, void *stream)
     hipStream_t st = zk_dec_stream(e, c, stream);
     zk_dec_args b = a;
     b.alone = !e->slot_busy[1];                             // (a batch submitted on the other context would be its neighbour)
+    b.neighbour = e->slot_busy[1];
     int rc = zk_decode_enqueue(e, c, st, b);
     if (rc) return rc;
     return zk_decode_finish(e, c, st);
@@ -417,6 +418,7 @@ extern "C" int zk_decode_submit_dev(zk_engine *e, const void *d_comp, uint64_t c
     zk_engine::DecCtx &c = e->dctx[slot];
     zk_profiling_off quiet(e);                              // per-kernel events belong to the synchronous path
     zk_dec_args a{d_comp, comp_size, d_c_off, d_d_off, first, count, nullptr, nullptr, d_dst, dst_cap, verify, d_frame_status, nullptr, 0};
+    a.neighbour = e->slot_busy[slot ^ 1];                   // (the first batch of a pipeline, or one submitted and waited for alone, has none)
     int rc = zk_decode_enqueue(e, c, c.st, a);
     if (rc) { (void)hipStreamSynchronize(c.st); return rc; }
     e->slot_busy[slot] = true;
