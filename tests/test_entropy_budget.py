@@ -77,3 +77,12 @@ def test_the_executor_pad_means_four_per_cu(kernels):
     x = int(_one(kernels, "_Z9zk_k_execILi256ELb0ELi2ELb0EE")["group_segment_fixed_size"])
     assert CU_LDS // x == 5
     assert CU_LDS // (x + EXEC_PAD) == 4
+
+
+def test_checksum_kernels_keep_their_registers(kernels):
+    """The register counts the comments in zk_decode.hip and zk_dec_plan.h rest on: zk_k_xxh64_lean and zk_k_xxh64_follow in 64 (what is
+    left on a SIMD beside four executor waves), zk_k_xxh64_wide within the allocation granule above its 78, zk_k_xxh64_fed<4> in 128."""
+    for prefix, most in (("_Z15zk_k_xxh64_lean", 64), ("_Z17zk_k_xxh64_follow", 64), ("_Z15zk_k_xxh64_wide", 80), ("_Z14zk_k_xxh64_fedILi4EE", 128)):
+        k = _one(kernels, prefix)
+        print(prefix, "vgpr", k["vgpr_count"])
+        assert int(k["vgpr_count"]) <= most, prefix

@@ -158,3 +158,42 @@ def test_checksums_beside_the_executor(engine):
             d_comp[at] = d_comp[at] ^ 4
     finally:
         engine.set_kernel_choice(reset=0)
+
+
+@pytest.mark.parametrize("nf", [8, 48])
+def test_followers_finish_a_ragged_tail(engine, nf):
+    """The last len % 32 bytes of a frame in the two kernels beside the executor.  A frame they hash wrongly is only marked as a mismatch
+    and verified again behind the executor, so nothing but `checksums_followed` shows a wrong tail there -- and the 1 MiB frames of
+    test_checksums_beside_the_executor have no tail.  Frames of 65536 + 13 bytes take one 8-byte, one 4-byte and one 1-byte step; 8 of
+    them go to zk_k_xxh64_follow1 (zk_xxh_follow_plan: up to 32 frames), 48 to zk_k_xxh64_follow.  Every frame is ragged: a followed
+    frame is a tail that came out right."""
+    import torch
+    dev = torch.device("cuda", 0)
+    fs = 65536 + 13
+    data = zko.gen_chunks(nf * fs, 0x7200 + nf)
+    comp, frames = engine.encode_frames(data, fs, 1, True)
+    assert len(frames) == nf
+    c, d = offsets_from_frames(frames)
+    d_comp = torch.from_numpy(np.frombuffer(comp + b"\0" * 64, np.uint8).copy()).to(dev)
+    d_c, d_d = torch.from_numpy(c.view(np.int64)).to(dev), torch.from_numpy(d.view(np.int64)).to(dev)
+    d_src = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
+    d_out = torch.zeros(nf * fs + 64, dtype=torch.uint8, device=dev)
+    d_st = torch.full((nf,), -1, dtype=torch.int32, device=dev)
+    engine.set_kernel_choice(reset=0)
+    try:
+        engine.set_kernel_choice(xxh64=4)
+        assert engine.decode_frames_dev(d_comp, len(comp), d_c, d_d, 0, nf, d_out, nf * fs, True, d_st) == 0
+        followed = engine.checksums_followed()
+        print("frames", nf, "followed", followed)
+        assert int(d_st.abs().sum().item()) == 0 and torch.equal(d_out[:nf * fs], d_src)
+        assert followed >= 1, followed
+        bad = 5
+        at = int(c[bad + 1]) - 1                              # the stored checksum's last byte
+        d_comp[at] = d_comp[at] ^ 4
+        rc = engine.decode_frames_dev(d_comp, len(comp), d_c, d_d, 0, nf, d_out, nf * fs, True, d_st)
+        st = d_st.cpu().numpy()
+        print("frames", nf, "followed with a damaged checksum", engine.checksums_followed())
+        assert rc < 0 and st[bad] == 22 and not np.delete(st, bad).any()
+        assert engine.checksums_followed() <= nf - 1          # never the damaged frame
+    finally:
+        engine.set_kernel_choice(reset=0)

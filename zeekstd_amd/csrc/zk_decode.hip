@@ -18,7 +18,15 @@
 //   zk_k_fse           the same with one lane per block (the form the CPU simulation of tests/sim mirrors; selectable)
 //   zk_k_exec          one workgroup per frame: byte-parallel sequence execution through a per-byte source map,
 //                      coalesced 16 B stores; optional raw-content prefix before the frame
-//   zk_k_xxh64         one wave per frame (4 accumulator chains), verifies Content_Checksum
+//   zk_k_xxh64         one wave per frame (4 accumulator chains), verifies Content_Checksum; its siblings for large batches (_wide, _fed,
+//                      _lean) and beside the executor (_follow, _follow1) differ in who runs the chains and share the seed, the
+//                      sixteen-frames-per-wave frame selection (zk_xxh64_lane) and the finalisation (zk_xxh64_finish)
+//
+// Code that sibling kernels have in common is a __forceinline__ helper beside them, not a copy: the shared-table sequence kernels (zk_k_fse_predef,
+// _predef_fed, zk_k_entropy_frame, zk_k_fse_sets) take their value tables, bitstream offsets, flush entries, feeder loop and block write-back
+// from zk_seq_values_to_lds, zk_fse_share_offset, zk_coop_enlist, zk_fse_feed and zk_fse_block_done.  tools/kdiff.py REV shows, kernel by
+// kernel, what such a change does to the code object (profiles/r10_fold_kdiff.txt).  Two kernels keep the machine code they had, to the byte,
+// and for that their own copies: zk_k_xxh64_wide (frame selection, tail) and zk_k_fse_predef_fed (flush entry, feeder loop) -- see there.
 //
 // No MFMA anywhere: this is byte-serial entropy decoding; the roofline is HBM (c_i + d_i bytes per frame).
 #include <hip/hip_runtime.h>
@@ -322,6 +330,26 @@ __global__ __launch_bounds__(128) void zk_k_huf(const uint8_t *comp, ZkBlock *bl
 }
 
 // ------------------------------------------------------------------------------------------------ FSE sequences
+// Shared by the sequence kernels below.  The literal-length and match-length value tables, copied into LDS by the workgroup's first 53
+// lanes (the caller's barrier follows).  (zk_fse_quad_group keeps its own form: baselines only for the narrow cells, and an offset table)
+__device__ __forceinline__ void zk_seq_values_to_lds(uint32_t tid, uint32_t *llv, uint32_t *mlv)
+{
+    const uint32_t ll_init[36] = ZK_LL_TABLE;
+    const uint32_t ml_init[53] = ZK_ML_TABLE;
+    if (tid < 36) llv[tid] = ll_init[tid];
+    if (tid < 53) mlv[tid] = ml_init[tid];
+}
+// What a finished sequence walk leaves in its block.  ZK_PAD_DONE: pad = 1, "done" -- what a shared-table kernel says, so that the per-block
+// kernel behind it skips the block; ZK_PAD_KEEP: the per-block kernels themselves, nobody comes behind them.
+constexpr bool ZK_PAD_DONE = true, ZK_PAD_KEEP = false;
+__device__ __forceinline__ void zk_fse_block_done(ZkBlock *o, const ZkBlock &b, bool mark)
+{
+    o->out_size = b.out_size;
+    o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
+    if (b.status != ZK_OK) o->status = b.status;      // (never OK over the literal kernel's, or the Huffman half's, verdict: the two run side by side)
+    if (mark) o->pad = 1;
+}
+
 // One lane per block, the block's LL / ML (2^9) and OF (2^8) tables + build scratch / record ring in LDS.  A block's
 // sequences are one serial chain (cells -> bit counts -> next states) of ~0.5 us per sequence, so the kernel's speed
 // is blocks in flight x instructions per sequence, and the table footprint sets the former:
@@ -336,12 +364,7 @@ __global__ __launch_bounds__(64 * ZK_FSE_WAVES) void zk_k_fse(const uint8_t *com
     __shared__ ZkSeqTablesT<CP> T[ZK_FSE_BLOCKS];
     __shared__ uint32_t llv[36], mlv[53];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {
-        const uint32_t ll_init[36] = ZK_LL_TABLE;
-        const uint32_t ml_init[53] = ZK_ML_TABLE;
-        if (tid < 36) llv[tid] = ll_init[tid];
-        if (tid < 53) mlv[tid] = ml_init[tid];
-    }
+    zk_seq_values_to_lds(tid, llv, mlv);
     __syncthreads();
     // gfx950 runs a wave with fewer than 16 active lanes ~3x slower per dependent instruction (measured:
     // tools/ubench/lat3.hip), so lanes 7..20 shadow lanes 0..6: same block, same LDS tables (broadcast
@@ -358,10 +381,7 @@ __global__ __launch_bounds__(64 * ZK_FSE_WAVES) void zk_k_fse(const uint8_t *com
                                                                                // had own tables too few neighbours share -- are taken here like any other)
     zk_decode_sequences<ZkRevU, CP>(comp, blocks, b, &T[slot], seqs + b.seq_base, llv, mlv, real);
     if (!real) return;
-    ZkBlock *o = &blocks[bi];
-    o->out_size = b.out_size;
-    o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
-    if (b.status != ZK_OK) o->status = b.status;      // (never OK over the literal kernel's verdict: the two run side by side)
+    zk_fse_block_done(&blocks[bi], b, ZK_PAD_KEEP);
 }
 
 // ---- three lanes per block ------------------------------------------------------------------------------------
@@ -501,10 +521,7 @@ __device__ __forceinline__ void zk_fse_quad_group(uint32_t group, const uint8_t 
             __builtin_amdgcn_s_sleep(1);
         }
         zk_seq_finish_block(b, cy, zk_lds_ld<uint32_t>(&s_wbad[slot]));
-        ZkBlock *o = &blocks[bi];
-        o->out_size = b.out_size;
-        o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
-        if (b.status != ZK_OK) o->status = b.status;      // (never OK over the literal kernel's verdict: the two run side by side)
+        zk_fse_block_done(&blocks[bi], b, ZK_PAD_KEEP);
         return;
     }
     // ---- the walker wave.  The three lanes build the block's tables together (identical LDS writes: more active lanes, see above)
@@ -615,14 +632,38 @@ __device__ __forceinline__ void zk_fse_share_build(const uint8_t *comp, const Zk
 #undef ZK_SHARE_TABLE
     sh->ok = ok;
 }
-// where the lane's bitstream starts: the defining block carries the descriptions itself
-__device__ __forceinline__ uint32_t zk_fse_share_offset(const ZkFsePick &p, uint32_t bi, const ZkBlock &b, const ZkFseShare *sh)
+// where the lane's bitstream starts: the defining block (key == its own index) carries the descriptions itself
+__device__ __forceinline__ uint32_t zk_fse_share_offset(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t bi, const ZkBlock &b, const ZkFseShare *sh)
 {
     uint32_t off = b.seq_off + 1;
-    if (p.k0 == bi) off += (uint32_t)sh->own[0];
-    if (p.k1 == bi) off += (uint32_t)sh->own[1];
-    if (p.k2 == bi) off += (uint32_t)sh->own[2];
+    if (k0 == bi) off += (uint32_t)sh->own[0];
+    if (k1 == bi) off += (uint32_t)sh->own[1];
+    if (k2 == bi) off += (uint32_t)sh->own[2];
     return off;
+}
+// The feeder wave's loop: aligned words of the lane's bitstream, last word first (ZkRevL::word_count / W(j)), into the lane's column of
+// the ring, never more than ZK_REVL_RING ahead of what the walker has taken; left when the walker wave says it is done.
+__device__ __forceinline__ void zk_fse_feed(const uint8_t *comp, const ZkBlock &b, uint32_t bs_off, uint32_t lane, ZkRevLShared *feed, uint32_t *done)
+{
+    const uint8_t *base = comp + b.src + bs_off;
+    const uint32_t len = b.bsize - bs_off, nwords = ZkRevL::word_count(base, len);
+    const uint8_t *ptr = reinterpret_cast<const uint8_t *>((((uintptr_t)base + len) + 7) & ~(uintptr_t)7) - 8;
+    uint32_t f = 0;
+    while (f < nwords && !zk_lds_ld<uint32_t>(done)) {
+        if (f - zk_lds_ld<uint32_t>(&feed->taken[lane]) < ZK_REVL_RING) {
+            const uint64_t w = *reinterpret_cast<const uint64_t *>(ptr);
+            zk_lds_st<uint64_t>(&feed->ring[f % ZK_REVL_RING][lane], w);
+            f++; ptr -= 8;
+            zk_lds_st<uint32_t>(&feed->filled[lane], f);
+        } else __builtin_amdgcn_s_sleep(1);
+    }
+}
+// a lane's entry in the cooperative flush: where its records go and how many there are (none for a lane that only helps storing)
+__device__ __forceinline__ void zk_coop_enlist(ZkCoopFlush *coop, uint32_t lane, bool active, const ZkBlock &b)
+{
+    coop->base[lane] = active ? b.seq_base : 0;
+    coop->nseq[lane] = active ? b.nseq : 0;
+    if (active) atomicMax(&coop->nloop, b.nseq);
 }
 
 template <typename RD>
@@ -634,13 +675,8 @@ __global__ __launch_bounds__(ZK_FSEP_LANES) void zk_k_fse_predef(const uint8_t *
     __shared__ ZkFseShare share;
     __shared__ uint32_t llv[36], mlv[53];
     const uint32_t tid = threadIdx.x;
-    {
-        const uint32_t ll_init[36] = ZK_LL_TABLE;
-        const uint32_t ml_init[53] = ZK_ML_TABLE;
-        if (tid < 36) llv[tid] = ll_init[tid];
-        if (tid < 53) mlv[tid] = ml_init[tid];
-        if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; share.ok = 0; }
-    }
+    zk_seq_values_to_lds(tid, llv, mlv);
+    if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; share.ok = 0; }
     __syncthreads();
     const uint32_t bi = blockIdx.x * ZK_FSEP_LANES + tid;
     ZkBlock b;
@@ -649,19 +685,13 @@ __global__ __launch_bounds__(ZK_FSEP_LANES) void zk_k_fse_predef(const uint8_t *
     if (!pk.go) return;                                    // nothing shared here (wave-uniform)
     if (tid < 16) zk_fse_share_build<ZkCells32>(comp, blocks, pk, &T, &share, llv, mlv);
     bool active = pk.match;
-    coop.base[tid] = active ? b.seq_base : 0;
-    coop.nseq[tid] = active ? b.nseq : 0;
-    if (active) atomicMax(&coop.nloop, b.nseq);
+    zk_coop_enlist(&coop, tid, active, b);
     __syncthreads();
     if (!share.ok) return;
     // every lane of the wave runs the walk in lock step (inactive ones only help storing the others' records)
-    zk_seq_walk<ZK_FSEP_RING, RD>(comp, b, active ? zk_fse_share_offset(pk, bi, b, &share) : 0, T.ll, T.of, T.ml, share.al, ring[tid], seqs, llv, mlv, true, &coop, active, tid);
+    zk_seq_walk<ZK_FSEP_RING, RD>(comp, b, active ? zk_fse_share_offset(pk.k0, pk.k1, pk.k2, bi, b, &share) : 0, T.ll, T.of, T.ml, share.al, ring[tid], seqs, llv, mlv, true, &coop, active, tid);
     if (!active) return;
-    ZkBlock *o = &blocks[bi];
-    o->out_size = b.out_size;
-    o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
-    if (b.status != ZK_OK) o->status = b.status;      // (never OK over the literal kernel's verdict: the two run side by side)
-    o->pad = 1;                                            // done: zk_k_fse_quad skips it
+    zk_fse_block_done(&blocks[bi], b, ZK_PAD_DONE);
 }
 
 // The same with a feeder wave: wave 0 walks (reader ZkRevL: stream words out of an LDS ring, no global load in the
@@ -680,14 +710,9 @@ __global__ __launch_bounds__(2 * ZK_FSEP_LANES) void zk_k_fse_predef_fed(const u
     __shared__ uint32_t llv[36], mlv[53], s_done;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const bool walker = tid < 64;
-    {
-        const uint32_t ll_init[36] = ZK_LL_TABLE;
-        const uint32_t ml_init[53] = ZK_ML_TABLE;
-        if (tid < 36) llv[tid] = ll_init[tid];
-        if (tid < 53) mlv[tid] = ml_init[tid];
-        if (walker) { feed.filled[lane] = 0; feed.taken[lane] = 0; }
-        if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; s_done = 0; share.ok = 0; }
-    }
+    zk_seq_values_to_lds(tid, llv, mlv);
+    if (walker) { feed.filled[lane] = 0; feed.taken[lane] = 0; }
+    if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; s_done = 0; share.ok = 0; }
     __syncthreads();
     const uint32_t bi = blockIdx.x * ZK_FSEP_LANES + lane;
     ZkBlock b;
@@ -696,25 +721,21 @@ __global__ __launch_bounds__(2 * ZK_FSEP_LANES) void zk_k_fse_predef_fed(const u
     if (!pk.go) return;
     if (tid < 16) zk_fse_share_build<ZkCells64>(comp, blocks, pk, &T, &share, llv, mlv);
     const bool active = pk.match;
-    if (walker) {
+    if (walker) {                                          // (zk_coop_enlist and, below, zk_fse_feed written out: this kernel keeps its code object, see zk_k_xxh64_wide)
         coop.base[lane] = active ? b.seq_base : 0;
         coop.nseq[lane] = active ? b.nseq : 0;
         if (active) atomicMax(&coop.nloop, b.nseq);
     }
     __syncthreads();
     if (!share.ok) return;
-    const uint32_t bs_off = active ? zk_fse_share_offset(pk, bi, b, &share) : 0;
+    const uint32_t bs_off = active ? zk_fse_share_offset(pk.k0, pk.k1, pk.k2, bi, b, &share) : 0;
     if (walker) {
         zk_seq_walk<ZK_FSEP_RING, ZkRevL, ZkCells64>(comp, b, bs_off, T.ll, T.of, T.ml, share.al, ring[lane], seqs, llv, mlv, true, &coop, active, lane, &feed);
         zk_lds_st<uint32_t>(&s_done, 1u);
         if (!active) return;
-        ZkBlock *o = &blocks[bi];
-        o->out_size = b.out_size;
-        o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
-        if (b.status != ZK_OK) o->status = b.status;      // (never OK over the literal kernel's verdict: the two run side by side)
-        o->pad = 1;
+        zk_fse_block_done(&blocks[bi], b, ZK_PAD_DONE);
     } else if (active && bs_off < b.bsize) {
-        // feeder: aligned words of the lane's bitstream, last word first (ZkRevL::word_count / W(j))
+        // feeder: zk_fse_feed, written out
         const uint8_t *base = comp + b.src + bs_off;
         const uint32_t len = b.bsize - bs_off, nwords = ZkRevL::word_count(base, len);
         const uint8_t *ptr = reinterpret_cast<const uint8_t *>((((uintptr_t)base + len) + 7) & ~(uintptr_t)7) - 8;
@@ -755,14 +776,9 @@ __global__ __launch_bounds__(4 * ZK_FSEP_LANES) void zk_k_entropy_frame(const ui
     __shared__ ZkPairBar bar;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const bool walker = tid < 64, fse_half = tid < 128;
-    {
-        const uint32_t ll_init[36] = ZK_LL_TABLE;
-        const uint32_t ml_init[53] = ZK_ML_TABLE;
-        if (tid < 36) llv[tid] = ll_init[tid];
-        if (tid < 53) mlv[tid] = ml_init[tid];
-        if (walker) { feed.filled[lane] = 0; feed.taken[lane] = 0; }
-        if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; s_done = 0; share.ok = 0; bar.n = 0; }
-    }
+    zk_seq_values_to_lds(tid, llv, mlv);
+    if (walker) { feed.filled[lane] = 0; feed.taken[lane] = 0; }
+    if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; s_done = 0; share.ok = 0; bar.n = 0; }
     __syncthreads();
     const uint32_t bi = blockIdx.x * ZK_FSEP_LANES + lane;
     ZkBlock b;
@@ -773,11 +789,7 @@ __global__ __launch_bounds__(4 * ZK_FSEP_LANES) void zk_k_entropy_frame(const ui
         pk = zk_fse_share_pick(nblocks, bi, b);                       // both waves, same verdict
         if (pk.go) {
             if (tid < 16) zk_fse_share_build<ZkCells64>(comp, blocks, pk, &T, &share, llv, mlv);
-            if (walker) {
-                coop.base[lane] = pk.match ? b.seq_base : 0;
-                coop.nseq[lane] = pk.match ? b.nseq : 0;
-                if (pk.match) atomicMax(&coop.nloop, b.nseq);
-            }
+            if (walker) zk_coop_enlist(&coop, lane, pk.match, b);
         }
     }
     __syncthreads();                                                  // the last barrier of the whole workgroup
@@ -791,31 +803,13 @@ __global__ __launch_bounds__(4 * ZK_FSEP_LANES) void zk_k_entropy_frame(const ui
     }
     if (!pk.go || !share.ok) return;                                  // blocks left with pad == 0: the pass behind this kernel takes them
     const bool active = pk.match;
-    const uint32_t bs_off = active ? zk_fse_share_offset(pk, bi, b, &share) : 0;
+    const uint32_t bs_off = active ? zk_fse_share_offset(pk.k0, pk.k1, pk.k2, bi, b, &share) : 0;
     if (walker) {
         zk_seq_walk<ZK_FSEP_RING, ZkRevL, ZkCells64>(comp, b, bs_off, T.ll, T.of, T.ml, share.al, ring[lane], seqs, llv, mlv, true, &coop, active, lane, &feed);
         zk_lds_st<uint32_t>(&s_done, 1u);
         if (!active) return;
-        ZkBlock *o = &blocks[bi];
-        o->out_size = b.out_size;
-        o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
-        if (b.status != ZK_OK) o->status = b.status;      // (never OK over the Huffman half's verdict: the two run side by side)
-        o->pad = 1;
-    } else if (active && bs_off < b.bsize) {
-        // feeder: as in zk_k_fse_predef_fed
-        const uint8_t *base = comp + b.src + bs_off;
-        const uint32_t len = b.bsize - bs_off, nwords = ZkRevL::word_count(base, len);
-        const uint8_t *ptr = reinterpret_cast<const uint8_t *>((((uintptr_t)base + len) + 7) & ~(uintptr_t)7) - 8;
-        uint32_t f = 0;
-        while (f < nwords && !zk_lds_ld<uint32_t>(&s_done)) {
-            if (f - zk_lds_ld<uint32_t>(&feed.taken[lane]) < ZK_REVL_RING) {
-                const uint64_t w = *reinterpret_cast<const uint64_t *>(ptr);
-                zk_lds_st<uint64_t>(&feed.ring[f % ZK_REVL_RING][lane], w);
-                f++; ptr -= 8;
-                zk_lds_st<uint32_t>(&feed.filled[lane], f);
-            } else __builtin_amdgcn_s_sleep(1);
-        }
-    }
+        zk_fse_block_done(&blocks[bi], b, ZK_PAD_DONE);
+    } else if (active && bs_off < b.bsize) zk_fse_feed(comp, b, bs_off, lane, &feed, &s_done);
 }
 
 // Several table sets per workgroup.  The kernels above serve ONE set per 64 consecutive blocks, which is a whole frame only
@@ -859,14 +853,9 @@ __global__ __launch_bounds__(ZK_FSEP_LANES) void zk_k_fse_sets(const uint8_t *co
     __shared__ ZkFseShare share[ZK_FSEP_SETS];
     __shared__ uint32_t llv[36], mlv[53];
     const uint32_t tid = threadIdx.x;
-    {
-        const uint32_t ll_init[36] = ZK_LL_TABLE;
-        const uint32_t ml_init[53] = ZK_ML_TABLE;
-        if (tid < 36) llv[tid] = ll_init[tid];
-        if (tid < 53) mlv[tid] = ml_init[tid];
-        if (tid < (uint32_t)ZK_FSEP_SETS) share[tid].ok = 0;
-        if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; }
-    }
+    zk_seq_values_to_lds(tid, llv, mlv);
+    if (tid < (uint32_t)ZK_FSEP_SETS) share[tid].ok = 0;
+    if (tid == 0) { coop.ring = &ring[0][0]; coop.seqs = seqs; coop.nloop = 0; }
     __syncthreads();
     const uint32_t bi = blockIdx.x * ZK_FSEP_LANES + tid;
     ZkBlock b;
@@ -885,25 +874,13 @@ __global__ __launch_bounds__(ZK_FSEP_LANES) void zk_k_fse_sets(const uint8_t *co
     __syncthreads();
     const uint32_t ms = pk.set < 0 ? 0u : (uint32_t)pk.set;
     const bool active = pk.set >= 0 && share[ms].ok;       // a damaged description: zk_k_fse_quad reports it block by block
-    coop.base[tid] = active ? b.seq_base : 0;
-    coop.nseq[tid] = active ? b.nseq : 0;
-    if (active) atomicMax(&coop.nloop, b.nseq);
+    zk_coop_enlist(&coop, tid, active, b);
     if (!__syncthreads_or(active)) return;
-    uint32_t bs_off = 0;
-    if (active) {
-        bs_off = b.seq_off + 1;
-        if (pk.k0 == bi) bs_off += (uint32_t)share[ms].own[0];
-        if (pk.k1 == bi) bs_off += (uint32_t)share[ms].own[1];
-        if (pk.k2 == bi) bs_off += (uint32_t)share[ms].own[2];
-    }
+    const uint32_t bs_off = active ? zk_fse_share_offset(pk.k0, pk.k1, pk.k2, bi, b, &share[ms]) : 0;
     // every lane of the wave runs the walk in lock step (inactive ones only help storing the others' records)
     zk_seq_walk<ZK_FSEP_RING, ZkRevU>(comp, b, bs_off, T[ms].ll, T[ms].of, T[ms].ml, share[ms].al, ring[tid], seqs, llv, mlv, true, &coop, active, tid);
     if (!active) return;
-    ZkBlock *o = &blocks[bi];
-    o->out_size = b.out_size;
-    o->rep_out[0] = b.rep_out[0]; o->rep_out[1] = b.rep_out[1]; o->rep_out[2] = b.rep_out[2];
-    if (b.status != ZK_OK) o->status = b.status;      // (never OK over the literal kernel's verdict: the two run side by side)
-    o->pad = 1;                                            // done: zk_k_fse_quad skips it
+    zk_fse_block_done(&blocks[bi], b, ZK_PAD_DONE);
 }
 
 // ------------------------------------------------------------------------------------------------ sequence execution
@@ -1916,6 +1893,49 @@ __device__ __forceinline__ uint64_t zk_rotl64(uint64_t x, int r)
 constexpr uint64_t XP1 = 0x9E3779B185EBCA87ull, XP2 = 0xC2B2AE3D27D4EB4Full, XP3 = 0x165667B19E3779F9ull,
                    XP4 = 0x85EBCA77C2B2AE63ull, XP5 = 0x27D4EB2F165667C5ull;
 __device__ __forceinline__ uint64_t zk_xround(uint64_t acc, uint64_t x) { return zk_rotl64(acc + x * XP2, 31) * XP1; }
+// accumulator kl (0..3) before the first stripe.  (A macro: as an inlined function the same expression changes the register allocation of
+// the double-batch loops -- zk_k_xxh64_lean 68 -> 72 bytes of scratch, zk_k_xxh64_follow 64 -> 61 registers, zk_k_xxh64_wide and _fed rescheduled)
+#define ZK_XXH64_SEED(kl) ((kl) == 0 ? XP1 + XP2 : (kl) == 1 ? XP2 : (kl) == 2 ? 0 : 0 - XP1)
+// the hash of a frame from its four accumulators behind the last whole stripe: their merge, the tail of len % 32 bytes (8, 4, 1 at a
+// time) and the avalanche.  Once per frame, in one lane; every XXH64 kernel below ends here.
+__device__ __forceinline__ uint64_t zk_xxh64_finish(uint64_t v1, uint64_t v2, uint64_t v3, uint64_t v4, const uint8_t *p, uint64_t len, uint64_t nstripes)
+{
+    uint64_t h;
+    if (len >= 32) {
+        h = zk_rotl64(v1, 1) + zk_rotl64(v2, 7) + zk_rotl64(v3, 12) + zk_rotl64(v4, 18);
+        h = (h ^ zk_xround(0, v1)) * XP1 + XP4;
+        h = (h ^ zk_xround(0, v2)) * XP1 + XP4;
+        h = (h ^ zk_xround(0, v3)) * XP1 + XP4;
+        h = (h ^ zk_xround(0, v4)) * XP1 + XP4;
+    } else h = XP5;
+    h += len;
+    const uint8_t *t = p + (nstripes << 5), *end = p + len;
+    while (t + 8 <= end) { h ^= zk_xround(0, zk_ld64(t)); h = zk_rotl64(h, 27) * XP1 + XP4; t += 8; }
+    if (t + 4 <= end) { h ^= (uint64_t)zk_rd32(t) * XP1; h = zk_rotl64(h, 23) * XP2 + XP3; t += 4; }
+    while (t < end) { h ^= (uint64_t)(*t) * XP5; h = zk_rotl64(h, 11) * XP1; t++; }
+    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
+    return h;
+}
+// Sixteen frames per wave, lane = (frame f, accumulator): which frame is this lane's, and where the wave's frames stop having stripes
+// in common.  live: f is in range, checksummed and OK (infos may be null: hash everything), and not already verified by zk_k_xxh64_follow
+// (skip may be null).  least: the fewest stripes of a live frame among the wave's lanes, ~0 when the wave has no frame to hash.
+struct ZkXxhLane { bool live; const uint8_t *p; uint64_t len, nstripes, least; };
+__device__ __forceinline__ ZkXxhLane zk_xxh64_lane(bool in_range, uint32_t f, const uint8_t *data, const uint64_t *d_off, uint32_t first,
+                                                   const ZkFrameInfo *infos, const uint64_t *skip)
+{
+    ZkXxhLane x;
+    x.live = in_range;
+    if (x.live && infos && !(infos[f].status == ZK_OK && infos[f].checksum_flag)) x.live = false;
+    if (x.live && skip && (skip[f] & ZK_PROG_VERIFIED)) x.live = false;
+    const uint32_t fa = x.live ? f : 0;                     // (a lane without a frame reads frame 0 and keeps nothing)
+    x.p = data + (d_off[first + fa] - d_off[first]);
+    x.len = d_off[first + fa + 1] - d_off[first + fa];
+    x.nstripes = x.live ? x.len >> 5 : 0;
+    x.least = x.live ? x.nstripes : ~0ull;
+#pragma unroll
+    for (int m = 4; m < 64; m <<= 1) { const uint64_t o = __shfl_xor(x.least, m, 64); x.least = o < x.least ? o : x.least; }
+    return x;
+}
 
 // One wave per frame.  All 64 lanes stream the frame in 1 KiB chunks (coalesced 16 B loads, one chunk
 // in flight ahead) and pre-multiply every word by P2; the products go through LDS to lanes 0-3, which
@@ -1931,7 +1951,7 @@ __global__ __launch_bounds__(64) void zk_k_xxh64(const uint8_t *data, const uint
     const uint64_t nchunks = len >> 10;
     // lanes 4..15 shadow lanes 0..3: a wave with < 16 active lanes runs ~3x slower on gfx950 (tools/ubench/lat3.hip)
     const uint32_t kl = lane & 3;
-    uint64_t acc = kl == 0 ? XP1 + XP2 : kl == 1 ? XP2 : kl == 2 ? 0 : 0 - XP1;
+    uint64_t acc = ZK_XXH64_SEED(kl);
     const bool aligned = (((uintptr_t)p) & 15) == 0;
     uint64_t a = 0, b = 0;
     auto ldpair = [&](uint64_t c) {
@@ -1955,20 +1975,7 @@ __global__ __launch_bounds__(64) void zk_k_xxh64(const uint8_t *data, const uint
     if (lane < 16) for (uint64_t i = nchunks << 5; i < nstripes; i++) acc = zk_xround(acc, zk_ld64(p + (i << 5) + 8 * kl));
     uint64_t v1 = __shfl(acc, 0, 64), v2 = __shfl(acc, 1, 64), v3 = __shfl(acc, 2, 64), v4 = __shfl(acc, 3, 64);
     if (lane != 0) return;
-    uint64_t h;
-    if (len >= 32) {
-        h = zk_rotl64(v1, 1) + zk_rotl64(v2, 7) + zk_rotl64(v3, 12) + zk_rotl64(v4, 18);
-        h = (h ^ zk_xround(0, v1)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v2)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v3)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v4)) * XP1 + XP4;
-    } else h = XP5;
-    h += len;
-    const uint8_t *t = p + (nstripes << 5), *end = p + len;
-    while (t + 8 <= end) { h ^= zk_xround(0, zk_ld64(t)); h = zk_rotl64(h, 27) * XP1 + XP4; t += 8; }
-    if (t + 4 <= end) { h ^= (uint64_t)zk_rd32(t) * XP1; h = zk_rotl64(h, 23) * XP2 + XP3; t += 4; }
-    while (t < end) { h ^= (uint64_t)(*t) * XP5; h = zk_rotl64(h, 11) * XP1; t++; }
-    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
+    const uint64_t h = zk_xxh64_finish(v1, v2, v3, v4, p, len, nstripes);
     if (hashes) hashes[f] = h;
     if (infos && (uint32_t)h != infos[f].checksum) infos[f].status = ZK_E_CHECKSUM_WRONG;
 }
@@ -1978,6 +1985,10 @@ __global__ __launch_bounds__(64) void zk_k_xxh64(const uint8_t *data, const uint
 // slots on 4 (16) lanes -- 1.7 G wave instructions per 4 GiB, a twelfth of what the encoder's matcher issues, and whichever kernel
 // runs beside the checksums pays for them (the entropy stage: 6.3 -> 7.6 ms).  Here the same chains cost a sixteenth of that:
 // 128 waves for 2048 frames, a lane loading its own 8 bytes of every stripe, 24 stripes per batch, two batches under way.
+// (Its own frame selection and tail, not zk_xxh64_lane / zk_xxh64_finish, and zk_fse_share_pick its own keys: with the helpers this kernel's
+// epilogue and zk_k_fse_predef_fed's prologue and feeder set-up were compiled differently, and a generated-frames decode through those two
+// kernels ended once in a HIP queue error on the device whose cause was not found.  Both keep the code object they had, byte for byte,
+// until it is: profiles/r10_fold_kdiff.txt.)
 constexpr int ZK_XXW = 24;
 __global__ __launch_bounds__(64) void zk_k_xxh64_wide(const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count,
                                                       ZkFrameInfo *infos, uint64_t *hashes, const uint64_t *skip)
@@ -2059,27 +2070,18 @@ __global__ __launch_bounds__(64 * (1 + (NF >= 8 ? NF / 8 : 1))) void zk_k_xxh64_
     __shared__ __attribute__((aligned(16))) uint8_t ring[2][ZK_XF_CHUNK * ZK_XF_ROW];
     const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t f = blockIdx.x * NF + (lane >> 2), kl = lane & 3;
-    bool live = lane < 4 * NF && f < count;
-    if (live && infos && !(infos[f].status == ZK_OK && infos[f].checksum_flag)) live = false;
-    if (live && skip && (skip[f] & ZK_PROG_VERIFIED)) live = false;       // zk_k_xxh64_follow has verified this frame
-    const uint32_t fa = live ? f : 0;                       // (a lane without a frame reads frame 0 and keeps nothing)
-    const uint8_t *p = data + (d_off[first + fa] - d_off[first]);
-    const uint64_t len = d_off[first + fa + 1] - d_off[first + fa];
-    const uint64_t nstripes = live ? len >> 5 : 0;
-    uint64_t least = live ? nstripes : ~0ull;
-    bool ragged = (((uintptr_t)p) & 15) != 0;
-#pragma unroll
-    for (int m = 4; m < 64; m <<= 1) { const uint64_t o = __shfl_xor(least, m, 64); least = o < least ? o : least; }
-    if (least == ~0ull) return;                             // no frame to hash in this workgroup (every wave finds the same)
+    const ZkXxhLane x = zk_xxh64_lane(lane < 4 * NF && f < count, f, data, d_off, first, infos, skip);
+    bool ragged = (((uintptr_t)x.p) & 15) != 0;
+    if (x.least == ~0ull) return;                           // no frame to hash in this workgroup (every wave finds the same)
     const bool any_ragged = __any(ragged);
-    const uint64_t nchunks = least / ZK_XF_CHUNK;            // the chunks every live frame of the group has
+    const uint64_t nchunks = x.least / ZK_XF_CHUNK;          // the chunks every live frame of the group has
     if (wave != 0) {
         // producers: frames PF (wave - 1) ... of the group; the frame's pointer sits in lane 4 j of the consumer's layout
         const uint32_t j0 = PF * (wave - 1);
         const uint8_t *pj[PF];
 #pragma unroll
         for (int j = 0; j < PF; j++) {
-            const uint64_t a = (uint64_t)(uintptr_t)p;
+            const uint64_t a = (uint64_t)(uintptr_t)x.p;
             pj[j] = (const uint8_t *)(uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(a >> 32), 4 * (int)(j0 + j)) << 32) |
                                                  (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)a, 4 * (int)(j0 + j)));
         }
@@ -2121,7 +2123,7 @@ __global__ __launch_bounds__(64 * (1 + (NF >= 8 ? NF / 8 : 1))) void zk_k_xxh64_
         return;
     }
     // the chains
-    uint64_t acc = kl == 0 ? XP1 + XP2 : kl == 1 ? XP2 : kl == 2 ? 0 : 0 - XP1;
+    uint64_t acc = ZK_XXH64_SEED(kl);
     for (uint64_t k = 0; k < nchunks; k++) {
         __syncthreads();
         if (lane < 4 * NF) {                                 // (NF = 4: sixteen lanes at work -- an instruction of the chain takes one pass of the SIMD, not four)
@@ -2131,52 +2133,32 @@ __global__ __launch_bounds__(64 * (1 + (NF >= 8 ? NF / 8 : 1))) void zk_k_xxh64_
         }
     }
     // what is left of the longer frames, stripe by stripe
-    const uint8_t *q = p + 8 * kl;
-    for (uint64_t i = nchunks * ZK_XF_CHUNK; i < nstripes; i++) acc = zk_xround(acc, zk_ld64(q + (i << 5)));
+    const uint8_t *q = x.p + 8 * kl;
+    for (uint64_t i = nchunks * ZK_XF_CHUNK; i < x.nstripes; i++) acc = zk_xround(acc, zk_ld64(q + (i << 5)));
     const uint32_t base = lane & ~3u;
     const uint64_t v1 = __shfl(acc, base, 64), v2 = __shfl(acc, base + 1, 64), v3 = __shfl(acc, base + 2, 64), v4 = __shfl(acc, base + 3, 64);
-    if (kl != 0 || !live) return;
-    uint64_t h;
-    if (len >= 32) {
-        h = zk_rotl64(v1, 1) + zk_rotl64(v2, 7) + zk_rotl64(v3, 12) + zk_rotl64(v4, 18);
-        h = (h ^ zk_xround(0, v1)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v2)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v3)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v4)) * XP1 + XP4;
-    } else h = XP5;
-    h += len;
-    const uint8_t *t = p + (nstripes << 5), *end = p + len;
-    while (t + 8 <= end) { h ^= zk_xround(0, zk_ld64(t)); h = zk_rotl64(h, 27) * XP1 + XP4; t += 8; }
-    if (t + 4 <= end) { h ^= (uint64_t)zk_rd32(t) * XP1; h = zk_rotl64(h, 23) * XP2 + XP3; t += 4; }
-    while (t < end) { h ^= (uint64_t)(*t) * XP5; h = zk_rotl64(h, 11) * XP1; t++; }
-    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
+    if (kl != 0 || !x.live) return;
+    const uint64_t h = zk_xxh64_finish(v1, v2, v3, v4, x.p, x.len, x.nstripes);
     if (hashes) hashes[f] = h;
     if (infos && (uint32_t)h != infos[f].checksum) infos[f].status = ZK_E_CHECKSUM_WRONG;
 }
 
 // The same in 64 registers (12 stripes per batch under waves_per_eu(8); zk_k_xxh64_wide takes 78): what is left on a SIMD beside four
 // executor waves of 112, so that the checksums of one batch can run while the executor of the next batch in flight holds the CUs --
-// with 78 the checksum waves of batch A wait until executor workgroups of batch B retire.  (A template only for this kernel: the
-// same body as a template under zk_k_xxh64_wide made the compiler take 122 registers there.)
+// with 78 the checksum waves of batch A wait until executor workgroups of batch B retire.  (A template only for this kernel.  The two
+// double-batch loops stay two: zk_k_xxh64_wide as zk_xxh64_lean_body<24> with `skip` takes 121 registers instead of its 78 -- measured
+// again with the frame selection and the tail shared, which is all the two have in common.)
 template <int ZK_XXW>
 __device__ __forceinline__ void zk_xxh64_lean_body(const uint8_t *data, const uint64_t *d_off, uint32_t first, uint32_t count,
                                                     ZkFrameInfo *infos, uint64_t *hashes)
 {
     const uint32_t lane = threadIdx.x, f = blockIdx.x * 16 + (lane >> 2), kl = lane & 3;
-    bool live = f < count;
-    if (live && infos && !(infos[f].status == ZK_OK && infos[f].checksum_flag)) live = false;
-    const uint32_t fa = live ? f : 0;                       // (a lane without a frame reads frame 0 and keeps nothing)
-    const uint8_t *p = data + (d_off[first + fa] - d_off[first]);
-    const uint64_t len = d_off[first + fa + 1] - d_off[first + fa];
-    const uint64_t nstripes = live ? len >> 5 : 0;
-    uint64_t acc = kl == 0 ? XP1 + XP2 : kl == 1 ? XP2 : kl == 2 ? 0 : 0 - XP1;
+    const ZkXxhLane x = zk_xxh64_lane(f < count, f, data, d_off, first, infos, nullptr);
+    uint64_t acc = ZK_XXH64_SEED(kl);
     // the stripes every live frame of the wave has, in whole double batches: no predicates
-    uint64_t least = live ? nstripes : ~0ull;
-#pragma unroll
-    for (int m = 4; m < 64; m <<= 1) { const uint64_t o = __shfl_xor(least, m, 64); least = o < least ? o : least; }
-    if (least == ~0ull) return;                             // no frame to hash in this wave
-    const uint64_t common = least - least % (2 * ZK_XXW);
-    const uint8_t *q = p + 8 * kl;
+    if (x.least == ~0ull) return;                           // no frame to hash in this wave
+    const uint64_t common = x.least - x.least % (2 * ZK_XXW);
+    const uint8_t *q = x.p + 8 * kl;
     uint64_t wa[ZK_XXW], wb[ZK_XXW];
     if (common) {
 #pragma unroll
@@ -2194,24 +2176,11 @@ __device__ __forceinline__ void zk_xxh64_lean_body(const uint8_t *data, const ui
         }
     }
     // what is left of the longer frames, stripe by stripe
-    for (uint64_t i = common; i < nstripes; i++) acc = zk_xround(acc, zk_ld64(q + (i << 5)));
+    for (uint64_t i = common; i < x.nstripes; i++) acc = zk_xround(acc, zk_ld64(q + (i << 5)));
     const uint32_t base = lane & ~3u;
     const uint64_t v1 = __shfl(acc, base, 64), v2 = __shfl(acc, base + 1, 64), v3 = __shfl(acc, base + 2, 64), v4 = __shfl(acc, base + 3, 64);
-    if (kl != 0 || !live) return;
-    uint64_t h;
-    if (len >= 32) {
-        h = zk_rotl64(v1, 1) + zk_rotl64(v2, 7) + zk_rotl64(v3, 12) + zk_rotl64(v4, 18);
-        h = (h ^ zk_xround(0, v1)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v2)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v3)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v4)) * XP1 + XP4;
-    } else h = XP5;
-    h += len;
-    const uint8_t *t = p + (nstripes << 5), *end = p + len;
-    while (t + 8 <= end) { h ^= zk_xround(0, zk_ld64(t)); h = zk_rotl64(h, 27) * XP1 + XP4; t += 8; }
-    if (t + 4 <= end) { h ^= (uint64_t)zk_rd32(t) * XP1; h = zk_rotl64(h, 23) * XP2 + XP3; t += 4; }
-    while (t < end) { h ^= (uint64_t)(*t) * XP5; h = zk_rotl64(h, 11) * XP1; t++; }
-    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
+    if (kl != 0 || !x.live) return;
+    const uint64_t h = zk_xxh64_finish(v1, v2, v3, v4, x.p, x.len, x.nstripes);
     if (hashes) hashes[f] = h;
     if (infos && (uint32_t)h != infos[f].checksum) infos[f].status = ZK_E_CHECKSUM_WRONG;
 }
@@ -2269,7 +2238,7 @@ __device__ __forceinline__ void zk_xxh64_follow_body(const uint8_t *data, const 
     const uint8_t *p = data + (d_off[first + fa] - d_off[first]);
     const uint64_t len = d_off[first + fa + 1] - d_off[first + fa];
     const uint32_t nstripes = live ? (uint32_t)(len >> 5) : 0;
-    uint64_t acc = kl == 0 ? XP1 + XP2 : kl == 1 ? XP2 : kl == 2 ? 0 : 0 - XP1;
+    uint64_t acc = ZK_XXH64_SEED(kl);
     auto wave_min = [](uint32_t v) {
 #pragma unroll
         for (int m = 1; m < 64; m <<= 1) { const uint32_t o = __shfl_xor(v, m, 64); v = o < v ? o : v; }
@@ -2337,20 +2306,7 @@ __device__ __forceinline__ void zk_xxh64_follow_body(const uint8_t *data, const 
     const uint32_t base = lane & ~3u;
     const uint64_t v1 = __shfl(acc, base, 64), v2 = __shfl(acc, base + 1, 64), v3 = __shfl(acc, base + 2, 64), v4 = __shfl(acc, base + 3, 64);
     if (kl != 0 || !live) return;
-    uint64_t h;
-    if (len >= 32) {
-        h = zk_rotl64(v1, 1) + zk_rotl64(v2, 7) + zk_rotl64(v3, 12) + zk_rotl64(v4, 18);
-        h = (h ^ zk_xround(0, v1)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v2)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v3)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v4)) * XP1 + XP4;
-    } else h = XP5;
-    h += len;
-    const uint8_t *t = p + ((uint64_t)nstripes << 5), *end = p + len;
-    while (t + 8 <= end) { h ^= zk_xround(0, zk_ld64(t)); h = zk_rotl64(h, 27) * XP1 + XP4; t += 8; }
-    if (t + 4 <= end) { h ^= (uint64_t)zk_rd32(t) * XP1; h = zk_rotl64(h, 23) * XP2 + XP3; t += 4; }
-    while (t < end) { h ^= (uint64_t)(*t) * XP5; h = zk_rotl64(h, 11) * XP1; t++; }
-    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
+    const uint64_t h = zk_xxh64_finish(v1, v2, v3, v4, p, len, nstripes);
     progress[f] |= (uint32_t)h == infos[f].checksum ? ZK_PROG_VERIFIED : ZK_PROG_MISMATCH;
 }
 
@@ -2399,7 +2355,7 @@ __global__ __launch_bounds__(64) void zk_k_xxh64_follow1(const uint8_t *data, co
     const uint64_t len = d_off[first + f + 1] - d_off[first + f];
     const uint64_t nchunks = len >> 10;
     const uint32_t kl = lane & 3;
-    uint64_t acc = kl == 0 ? XP1 + XP2 : kl == 1 ? XP2 : kl == 2 ? 0 : 0 - XP1;
+    uint64_t acc = ZK_XXH64_SEED(kl);
     const bool aligned = (((uintptr_t)p) & 15) == 0;
     uint64_t a = 0, b = 0;
     auto ldpair = [&](uint64_t c) {
@@ -2437,20 +2393,7 @@ __global__ __launch_bounds__(64) void zk_k_xxh64_follow1(const uint8_t *data, co
     if (lane < 16) for (uint64_t i = nchunks << 5; i < nstripes; i++) acc = zk_xround(acc, zk_ld64(p + (i << 5) + 8 * kl));
     uint64_t v1 = __shfl(acc, 0, 64), v2 = __shfl(acc, 1, 64), v3 = __shfl(acc, 2, 64), v4 = __shfl(acc, 3, 64);
     if (lane != 0) return;
-    uint64_t h;
-    if (len >= 32) {
-        h = zk_rotl64(v1, 1) + zk_rotl64(v2, 7) + zk_rotl64(v3, 12) + zk_rotl64(v4, 18);
-        h = (h ^ zk_xround(0, v1)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v2)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v3)) * XP1 + XP4;
-        h = (h ^ zk_xround(0, v4)) * XP1 + XP4;
-    } else h = XP5;
-    h += len;
-    const uint8_t *t = p + (nstripes << 5), *end = p + len;
-    while (t + 8 <= end) { h ^= zk_xround(0, zk_ld64(t)); h = zk_rotl64(h, 27) * XP1 + XP4; t += 8; }
-    if (t + 4 <= end) { h ^= (uint64_t)zk_rd32(t) * XP1; h = zk_rotl64(h, 23) * XP2 + XP3; t += 4; }
-    while (t < end) { h ^= (uint64_t)(*t) * XP5; h = zk_rotl64(h, 11) * XP1; t++; }
-    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
+    const uint64_t h = zk_xxh64_finish(v1, v2, v3, v4, p, len, nstripes);
     atomicOr((unsigned long long *)(progress + f), (uint32_t)h == infos[f].checksum ? ZK_PROG_VERIFIED : ZK_PROG_MISMATCH);
 }
 
