@@ -109,9 +109,12 @@ enum {
                                    * (zk_k_entropy_frame) for every batch that qualifies -- no frame with more than one set of own tables -- whatever its
                                    * size; 0 = by batch shape.  zk_engine_entropy_fused says which one ran */
     ZK_CHOICE_RANGE_PASS_MIB = 14, /* zk_read_ranges*: decoded MiB of scratch per pass (1..2^20; 0 = 1024).  A pass is never less than one frame */
-    ZK_CHOICE_ENC_DENSE_SLICE_KIB = 15 /* encodes with dense far history (level 0 / >= 3, frames beyond the matcher's ring): input KiB whose candidate scratch
+    ZK_CHOICE_ENC_DENSE_SLICE_KIB = 15, /* encodes with dense far history (level 0 / >= 3, frames beyond the matcher's ring): input KiB whose candidate scratch
                                         * (8 bytes per input byte) is reserved at a time (1..2^22; 0 = 2^22, 4 GiB).  A longer input is matched slice after
                                         * slice of whole frames over that scratch, never less than one frame; the bytes produced do not depend on it */
+    ZK_CHOICE_ENC_DICT_SLICE_KIB = 16  /* zk_encode_frames_dict*: KiB of [dictionary content | frame] records staged for the matcher at a time (1..2^22;
+                                        * 0 = 2^20, 1 GiB).  A longer input is staged and matched slice after slice of whole frames over that buffer, never
+                                        * less than one frame; the bytes produced do not depend on it */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -212,8 +215,8 @@ int zk_decode_frames_prefix(zk_engine *e, const uint8_t *comp, uint64_t comp_siz
  * An explicit non-empty prefix (zk_decode_frames_prefix*, zk_decoder_decompress_with_prefix) overrides the dictionary for that call, as
  * ZSTD_DCtx_refPrefix does.  As in libzstd, EVERY frame of the call starts from the dictionary's repeat offsets and has its content below it: a frame that was made without
  * a dictionary decodes to the same bytes unless it uses a repeat offset before it has set one (libzstd's encoder emits no such frame) and the
- * dictionary's offsets are not 1 / 4 / 8, or it is damaged.  Encoding against a
- * dictionary is not offered. */
+ * dictionary's offsets are not 1 / 4 / 8, or it is damaged.  The encode
+ * half is zk_cdict / zk_encode_frames_dict* below. */
 typedef struct zk_dict zk_dict;
 int zk_dict_create(const uint8_t *bytes, size_t len, zk_dict **out);
 void zk_dict_free(zk_dict *d);
@@ -299,6 +302,8 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *                                                                                                                   submitted with)
  *   zk_gather_seekable                                                              refused   refused   refused    (a collective waits for its peers)
  *   zk_encode_frames[_prefix][_dev], zk_raw_encoder_*, zk_encoder_*                 served    served    served     (scratch of their own)
+ *   zk_cdict_create / _free / _id, zk_encode_frames_dict[_dev],                     served    served    served     (the same; a zk_cdict is no decode state)
+ *     zk_raw_encoder_set_dictionary, zk_encoder_set_dictionary
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
  *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
@@ -307,7 +312,7 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *   zk_engine_destroy                                                               served    served    served     (completes the batches first; their buffers hold the
  *                                                                                                                   results, their return codes are lost)
  * Functions that take no engine and no handle opened on one (zk_dict_*, zk_seek_table_*, zk_serializer_*, zk_host_alloc / _free,
- * zk_compress_bound, zk_shard_range, zk_set_collective_library) do not depend on any of this. */
+ * zk_compress_bound, zk_compress_bound_dict, zk_shard_range, zk_set_collective_library) do not depend on any of this. */
 int zk_decode_submit_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off,
                          const void *d_d_off, uint32_t first, uint32_t count, void *d_dst, uint64_t dst_cap,
                          int verify, void *d_frame_status, int *slot_out);
@@ -361,6 +366,46 @@ int zk_encode_frames_prefix_dev(zk_engine *e, const void *d_src, uint64_t n, uin
 int zk_encode_frames_prefix(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum,
                             const uint8_t *prefix, uint64_t prefix_len, uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes,
                             uint32_t *d_sizes, uint32_t frames_cap, uint32_t *n_frames_out, uint64_t *written_out);
+
+/* Encode against a zstd dictionary (what the reference reaches through EncodeOptions::with_cctx / .cctx(), encode.rs:142-155, with a context the
+ * caller has loaded a dictionary into; ZSTD_CCtx_loadDictionary / ZSTD_CDict).  The frames decode with the same dictionary: here with
+ * zk_engine_set_dictionary, in libzstd with ZSTD_DCtx_loadDictionary / ZSTD_decompress_usingDict.
+ * zk_cdict is the compiled dictionary on the device, the counterpart of ZSTD_CDict: made once from a zk_dict (which may be freed right away), used by
+ * any number of calls; several may exist on one engine, and each belongs to the engine it was made on (ZK_ERR_ARGUMENT on another).  Creation uploads
+ * the content the matcher can reach (its last 2^27 - 1 bytes) and, for a formatted dictionary, builds and uploads the compression side of its four
+ * tables: the Huffman code from the tree description's weights, the three FSE tables from the normalised counts, with a cost per symbol.  Free it
+ * before the engine is destroyed and after the last call that uses it has returned.  There is no engine-wide "current encode dictionary":
+ * zk_encode_frames* and zk_encode_frames_prefix* behave the same whatever objects exist.
+ * Every frame of zk_encode_frames_dict[_dev] (cdict == NULL: ZK_ERR_ARGUMENT):
+ *   - header: what zk_encode_frames_prefix* writes for the same input with the dictionary's content as the prefix -- the window covers content +
+ *     frame -- plus a Dictionary_ID field of the smallest width (1 / 2 / 4 bytes) that holds the ID; no field for a raw-content dictionary (ID 0).
+ *     n == 0 makes one empty frame that carries the field.
+ *   - sequences and literals: exactly those of the prefix route (same records, same match kernels at every level, the same long-distance table for
+ *     content beyond the matcher's ring).  The matcher emits a repeat code only after a sequence of the same block, so the dictionary's three repeat
+ *     offsets never enter.
+ *   - sequence tables, per frame and per table (LL / OF / ML), the cheapest by estimate of: predefined; the frame's own under the conditions of the
+ *     other routes; the dictionary's -- Repeat_Mode in every block of the frame that has sequences, the first included -- which is legal only if it
+ *     gives every code the frame uses a probability.  Ties keep what the other routes would take.
+ *   - literals, first block of a frame only: a Treeless_Literals_Block under the dictionary's tree where that is smaller, in bytes produced, than
+ *     the block's own tree, raw and RLE; legal only if every literal has a weight.  Later blocks are coded as on the other routes, and a
+ *     first block that was stored as a Raw_Block or RLE_Block stays one.
+ * A raw-content dictionary offers neither choice: its frames are byte-identical to zk_encode_frames_prefix* with the dictionary's bytes as the prefix.
+ * dst_cap >= zk_compress_bound_dict(n, frame_size) = zk_compress_bound(n, frame_size) + 4 per frame always suffices: the largest Dictionary_ID field
+ * is the one thing a frame gains.  Nothing else grows: a block is stored raw unless its compressed form is smaller, a dictionary table replaces table
+ * descriptions (the one thing that lets a block outgrow its input) and adds none, and a Treeless section is taken only where it is smaller than the
+ * section it replaces.  -70 and "destination untouched" are as for zk_encode_frames_dev.
+ * The [content | frame] records are staged for the matcher in slices of whole frames over a bounded buffer (ZK_CHOICE_ENC_DICT_SLICE_KIB, 1 GiB by
+ * default), not in one piece as the prefix route stages them. */
+typedef struct zk_cdict zk_cdict;
+int zk_cdict_create(zk_engine *e, const zk_dict *d, zk_cdict **out);
+void zk_cdict_free(zk_cdict *c);
+uint32_t zk_cdict_id(const zk_cdict *c);            /* 0 for a raw-content dictionary */
+uint64_t zk_compress_bound_dict(uint64_t n, uint32_t frame_size);
+int zk_encode_frames_dict_dev(zk_engine *e, const void *d_src, uint64_t n, uint32_t frame_size, int level, int checksum, const zk_cdict *cdict,
+                              void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint32_t *n_frames, uint64_t *written, void *stream);
+int zk_encode_frames_dict(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum, const zk_cdict *cdict,
+                          uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint32_t frames_cap, uint32_t *n_frames,
+                          uint64_t *written);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside
@@ -542,6 +587,12 @@ int zk_raw_encoder_end_frame(zk_raw_encoder *r, uint8_t *out, size_t out_len, si
 zk_seek_table *zk_raw_encoder_seek_table(const zk_raw_encoder *r);                                    /* :487 (a copy) */
 void zk_raw_encoder_reset_frame(zk_raw_encoder *r);                                                   /* :501 */
 void zk_raw_encoder_reset_seek_table(zk_raw_encoder *r);                                              /* :524 */
+/* engine-specific (ZSTD_CCtx_loadDictionary on the context the reference is handed with with_cctx, :142-155): the frames this handle writes are
+ * encoded against the compiled dictionary (zk_encode_frames_dict above), under every policy; NULL = none.  There is no field for it in
+ * zk_encode_opts, whose layout is ABI.  Allowed while no frame is open and nothing is buffered; otherwise -60 (stage_wrong, as
+ * ZSTD_CCtx_loadDictionary) and nothing changes.  A non-empty explicit prefix on a call overrides the dictionary for the frames begun under
+ * it, as in libzstd.  The zk_cdict must belong to the handle's engine and outlive the handle's use of it. */
+int zk_raw_encoder_set_dictionary(zk_raw_encoder *r, const zk_cdict *cdict);
 /* Encoder<W>: W is a write callback (return 0 on success) = io::Write::write_all */
 typedef int (*zk_write_fn)(void *user, const uint8_t *data, size_t len);
 int zk_encoder_new(zk_engine *e, const zk_encode_opts *o, zk_write_fn write, void *user, zk_encoder **out);   /* with_opts :596 */
@@ -555,6 +606,7 @@ int64_t zk_encoder_compress(zk_encoder *e, const uint8_t *buf, size_t len);     
 int64_t zk_encoder_compress_with_prefix(zk_encoder *e, const uint8_t *buf, size_t len, const uint8_t *prefix, size_t plen); /* :641; the prefix buffer must stay valid and unchanged until the frames begun under it are out (end_frame / flush / finish) */
 int64_t zk_encoder_end_frame(zk_encoder *e);                                                          /* :704 */
 int zk_encoder_flush(zk_encoder *e);                                                                  /* io::Write::flush :796 */
+int zk_encoder_set_dictionary(zk_encoder *e, const zk_cdict *cdict);                                  /* as zk_raw_encoder_set_dictionary */
 int zk_encoder_finish(zk_encoder *e, int format, uint64_t *total);                                    /* finish_format :755 */
 uint64_t zk_encoder_written_compressed(const zk_encoder *e);                                          /* :615 */
 zk_seek_table *zk_encoder_seek_table(const zk_encoder *e);                                            /* :610 (a copy) */

@@ -90,6 +90,26 @@ impl Engine {
 }
 impl Drop for Engine { fn drop(&mut self) { unsafe { ffi::zk_engine_destroy(self.0) } } }
 
+/// A dictionary compiled for encoding on one engine (`zk_cdict`, the counterpart of `ZSTD_CDict`): what a caller of the reference loads into
+/// the context it hands to `EncodeOptions::with_cctx` (encode.rs:142-155; `ZSTD_CCtx_loadDictionary`).  Made once, used by any number of
+/// encoders of that engine through `EncodeOptions::dictionary`; it borrows the engine, so it cannot outlive it.
+pub struct EncodeDictionary<'a> { h: *mut ffi::ZkCDict, _e: core::marker::PhantomData<&'a Engine> }
+impl<'a> EncodeDictionary<'a> {
+    /// `bytes`: a formatted dictionary (magic 0xEC30A437) or raw content
+    pub fn new(engine: &'a Engine, bytes: &[u8]) -> Result<Self> {
+        let mut d = core::ptr::null_mut();
+        check(unsafe { ffi::zk_dict_create(bytes.as_ptr(), bytes.len(), &mut d) })?;
+        let mut h = core::ptr::null_mut();
+        let rc = unsafe { ffi::zk_cdict_create(engine.as_ptr(), d, &mut h) };
+        unsafe { ffi::zk_dict_free(d) };
+        check(rc)?;
+        Ok(EncodeDictionary { h, _e: core::marker::PhantomData })
+    }
+    /// the Dictionary_ID its frames carry (0: raw content, no field)
+    pub fn id(&self) -> u32 { unsafe { ffi::zk_cdict_id(self.h) } }
+}
+impl<'a> Drop for EncodeDictionary<'a> { fn drop(&mut self) { unsafe { ffi::zk_cdict_free(self.h) } } }
+
 /// seek_table.rs:228-241
 #[derive(Clone, Copy, PartialEq, Eq, Debug, Default)]
 pub enum Format { Head, #[default] Foot }
@@ -382,13 +402,16 @@ impl Default for FrameSizePolicy { fn default() -> Self { FrameSizePolicy::Uncom
 
 /// encode.rs:110-207
 #[derive(Default)]
-pub struct EncodeOptions<'a> { engine: Option<&'a Engine>, policy: FrameSizePolicy, checksum: bool, level: i32 }
+pub struct EncodeOptions<'a> { engine: Option<&'a Engine>, policy: FrameSizePolicy, checksum: bool, level: i32, dictionary: Option<&'a EncodeDictionary<'a>> }
 impl<'a> EncodeOptions<'a> {
     pub fn new() -> Self { Self::default() }                                                            // :129
     /// :136 -- upstream's fallible constructor creates the compression context; here the engine is created (or injected) when the
     /// encoder is made, so there is nothing that can fail yet
     pub fn try_new() -> Option<Self> { Some(Self::default()) }
     pub fn engine(mut self, e: &'a Engine) -> Self { self.engine = Some(e); self }                       // with_cctx :142
+    /// with_cctx (:142-155) with a context that holds a dictionary: every frame that begins without an explicit prefix is encoded against
+    /// `d`, which must have been made on the engine given with `engine` (a dictionary needs an injected engine)
+    pub fn dictionary(mut self, d: &'a EncodeDictionary<'a>) -> Self { self.dictionary = Some(d); self }
     pub fn frame_size_policy(mut self, p: FrameSizePolicy) -> Self { self.policy = p; self }             // :158
     pub fn checksum_flag(mut self, f: bool) -> Self { self.checksum = f; self }                          // :164
     pub fn compression_level(mut self, l: i32) -> Self { self.level = l; self }                          // :170
@@ -399,13 +422,17 @@ impl<'a> EncodeOptions<'a> {
     pub fn into_raw_encoder(self) -> Result<RawEncoder<'a>> {                                            // :180
         let mut h = core::ptr::null_mut();
         check(unsafe { ffi::zk_raw_encoder_new(self.engine.map_or(core::ptr::null_mut(), |e| e.as_ptr()), &self.raw(), &mut h) })?;
-        Ok(RawEncoder { h, _e: core::marker::PhantomData })
+        let r = RawEncoder { h, _e: core::marker::PhantomData };
+        if let Some(d) = self.dictionary { check(unsafe { ffi::zk_raw_encoder_set_dictionary(r.h, d.h) })?; }
+        Ok(r)
     }
     pub fn into_encoder<W: Write>(self, writer: W) -> Result<Encoder<'a, W>> {                           // :204
         let mut w = Box::new(writer);
         let mut h = core::ptr::null_mut();
         check(unsafe { ffi::zk_encoder_new(self.engine.map_or(core::ptr::null_mut(), |e| e.as_ptr()), &self.raw(), Some(write_cb::<W>), &mut *w as *mut W as *mut c_void, &mut h) })?;
-        Ok(Encoder { h, writer: w, _e: core::marker::PhantomData })
+        let e = Encoder { h, writer: w, _e: core::marker::PhantomData };
+        if let Some(d) = self.dictionary { check(unsafe { ffi::zk_encoder_set_dictionary(e.h, d.h) })?; }
+        Ok(e)
     }
 }
 unsafe extern "C" fn write_cb<W: Write>(user: *mut c_void, data: *const u8, len: usize) -> c_int {

@@ -74,6 +74,14 @@ _sig = {
     "zk_dict_id": (C.c_uint32, [_P]),
     "zk_dict_content_offset": (C.c_size_t, [_P]),
     "zk_engine_set_dictionary": (C.c_int, [_P, _P]),
+    "zk_cdict_create": (C.c_int, [_P, _P, C.POINTER(_P)]),
+    "zk_cdict_free": (None, [_P]),
+    "zk_cdict_id": (C.c_uint32, [_P]),
+    "zk_compress_bound_dict": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "zk_encode_frames_dict": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_int, _P, _P, C.c_uint64, _P, _P, C.c_uint32,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "zk_encode_frames_dict_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_int, _P, _P, C.c_uint64, _P, _P,
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

@@ -468,6 +468,7 @@ for _n, _r, _a in [
     ("zk_raw_encoder_end_frame", C.c_int, [_P, _P, C.c_size_t, _szp, _szp]),
     ("zk_raw_encoder_seek_table", _P, [_P]),
     ("zk_raw_encoder_reset_frame", None, [_P]), ("zk_raw_encoder_reset_seek_table", None, [_P]),
+    ("zk_raw_encoder_set_dictionary", C.c_int, [_P, _P]), ("zk_encoder_set_dictionary", C.c_int, [_P, _P]),
     ("zk_encoder_new", C.c_int, [_P, C.POINTER(zk_encode_opts), _WRITE_FN, _P, C.POINTER(_P)]),
     ("zk_encoder_free", None, [_P]),
     ("zk_encoder_compress", C.c_int64, [_P, _P, C.c_size_t]),
@@ -501,6 +502,7 @@ class EncodeOptions:                   # encode.rs:110-207
     def __init__(self):
         self._o = zk_encode_opts(0, 0, 0, 0, 0)
         self._engine = None
+        self._dictionary = None
 
     @staticmethod
     def new():
@@ -508,6 +510,12 @@ class EncodeOptions:                   # encode.rs:110-207
 
     def engine(self, e: Engine):       # with_cctx / cctx
         self._engine = e
+        return self
+
+    def dictionary(self, d):
+        """with_cctx with a context that holds a dictionary: frames that begin without an explicit prefix are encoded against the
+        EncodeDictionary d, which belongs to the engine given with .engine(); None = none"""
+        self._dictionary = d
         return self
 
     def frame_size_policy(self, p: FrameSizePolicy):
@@ -545,6 +553,14 @@ class RawEncoder:                      # encode.rs:209-545
         h = _P()
         _chk(lib.zk_raw_encoder_new(opts._engine._h if opts._engine else None, C.byref(opts._o), C.byref(h)))
         self._h = h
+        self._dictionary = None
+        if opts._dictionary is not None:
+            self.set_dictionary(opts._dictionary)
+
+    def set_dictionary(self, d):
+        """zk_raw_encoder_set_dictionary: allowed while no frame is open and nothing is buffered (Error -60 otherwise, nothing changes)"""
+        _chk(lib.zk_raw_encoder_set_dictionary(self._h, d._h if d is not None else None))
+        self._dictionary = d                # kept alive while the handle uses it
 
     @staticmethod
     def new():
@@ -616,6 +632,14 @@ class Encoder:                         # encode.rs:570-800
         h = _P()
         _chk(lib.zk_encoder_new(opts._engine._h if opts._engine else None, C.byref(opts._o), self._cb, None, C.byref(h)))
         self._h = h
+        self._dictionary = None
+        if opts._dictionary is not None:
+            self.set_dictionary(opts._dictionary)
+
+    def set_dictionary(self, d):
+        """zk_encoder_set_dictionary: allowed while no frame is open and nothing is gathered (Error -60 otherwise, nothing changes)"""
+        _chk(lib.zk_encoder_set_dictionary(self._h, d._h if d is not None else None))
+        self._dictionary = d
 
     @staticmethod
     def new(writer):

@@ -310,6 +310,7 @@ int zk_raw_encoder_end_frame(zk_raw_encoder *r, uint8_t *out, size_t out_len, si
 zk_seek_table *zk_raw_encoder_seek_table(const zk_raw_encoder *r) { return new (std::nothrow) zk_seek_table{r->r.seek_table()}; }
 void zk_raw_encoder_reset_frame(zk_raw_encoder *r) { r->r.reset_frame(); }
 void zk_raw_encoder_reset_seek_table(zk_raw_encoder *r) { r->r.reset_seek_table(); }
+int zk_raw_encoder_set_dictionary(zk_raw_encoder *r, const zk_cdict *cdict) { return !r ? ZK_ERR_ARGUMENT : r->r.set_dictionary(cdict) ? 0 : -60; }
 
 int zk_encoder_new(zk_engine *e, const zk_encode_opts *o, zk_write_fn write, void *user, zk_encoder **out)
 {
@@ -337,6 +338,7 @@ int64_t zk_encoder_end_frame(zk_encoder *e)
     return rc ? rc : n;
 }
 int zk_encoder_flush(zk_encoder *e) { return guard([&] { e->e.flush(); }); }
+int zk_encoder_set_dictionary(zk_encoder *e, const zk_cdict *cdict) { return !e ? ZK_ERR_ARGUMENT : e->e.set_dictionary(cdict) ? 0 : -60; }
 int zk_encoder_finish(zk_encoder *e, int format, uint64_t *total)
 {
     return guard([&] { uint64_t t = e->e.finish_format(format == ZK_FORMAT_HEAD ? Format::Head : Format::Foot); if (total) *total = t; });

@@ -39,9 +39,26 @@ RawEncoder::RawEncoder(RawEncoder &&o) noexcept
       frame_c_size_(o.frame_c_size_), frame_d_size_(o.frame_d_size_), seek_table_(std::move(o.seek_table_)),
       frame_in_(std::move(o.frame_in_)), pending_(std::move(o.pending_)), pending_pos_(o.pending_pos_), encoded_(o.encoded_),
       next_probe_(o.next_probe_), ratio_(o.ratio_), coarse_(o.coarse_), est_c_(o.est_c_), piece_start_(o.piece_start_),
-      frame_prefix_(o.frame_prefix_), frame_prefix_len_(o.frame_prefix_len_)
+      frame_prefix_(o.frame_prefix_), frame_prefix_len_(o.frame_prefix_len_), cdict_(o.cdict_)
 {
     o.engine_ = nullptr; o.owns_engine_ = false;
+}
+
+// Whole frames in host memory through Level A: a non-empty explicit prefix overrides the dictionary for the frames begun under it (as
+// ZSTD_CCtx_refPrefix does in libzstd), the dictionary applies to every other frame, and without either it is the plain call.
+static int encode_host_frames(zk_engine *e, const zk_cdict *cdict, const uint8_t *src, uint64_t n, uint32_t fs, int level, int checksum, const uint8_t *prefix,
+                              uint64_t prefix_len, uint8_t *dst, uint64_t dst_cap, uint32_t *c, uint32_t *d, uint32_t frames_cap, uint32_t *nf, uint64_t *written)
+{
+    if (cdict && !(prefix && prefix_len)) return zk_encode_frames_dict(e, src, n, fs, level, checksum, cdict, dst, dst_cap, c, d, frames_cap, nf, written);
+    return zk_encode_frames_prefix(e, src, n, fs, level, checksum, prefix, prefix ? prefix_len : 0, dst, dst_cap, c, d, frames_cap, nf, written);
+}
+static uint64_t host_bound(const zk_cdict *cdict, uint64_t n, uint32_t fs) { return cdict ? zk_compress_bound_dict(n, fs) : zk_compress_bound(n, fs); }
+
+bool RawEncoder::set_dictionary(const zk_cdict *cdict)
+{
+    if (frame_d_size_ || frame_c_size_ || encoded_ || !frame_in_.empty() || !pending_.empty()) return false;
+    cdict_ = cdict;
+    return true;
 }
 
 size_t RawEncoder::remaining_frame_size() const                                // encode.rs:528-535
@@ -69,11 +86,11 @@ void RawEncoder::encode_pending()
 {
     if (encoded_) return;
     const size_t n = frame_in_.size();
-    pending_.resize((size_t)zk_compress_bound(n, n ? (uint32_t)n : 1));
+    pending_.resize((size_t)host_bound(cdict_, n, n ? (uint32_t)n : 1));
     uint32_t c = 0, d = 0, nf = 0;
     uint64_t written = 0;
-    int rc = zk_encode_frames_prefix(engine_, frame_in_.data(), n, n ? (uint32_t)n : 1, level_, checksum_ ? 1 : 0, frame_prefix_,
-                                     frame_prefix_ ? frame_prefix_len_ : 0, pending_.data(), pending_.size(), &c, &d, 1, &nf, &written);
+    int rc = encode_host_frames(engine_, cdict_, frame_in_.data(), n, n ? (uint32_t)n : 1, level_, checksum_ ? 1 : 0, frame_prefix_,
+                                frame_prefix_ ? frame_prefix_len_ : 0, pending_.data(), pending_.size(), &c, &d, 1, &nf, &written);
     if (rc != 0) throw Error::from_engine_code(rc, zk_engine_last_hip_error(engine_));
     pending_.resize((size_t)written);
     pending_pos_ = 0;
@@ -268,7 +285,10 @@ void Encoder::encode_span(const uint8_t *src, size_t take)
     if (rc != 0) throw Error::from_engine_code(rc, zk_engine_last_hip_error(raw_.engine_));
     prefix_dirty_ = false;
     sink_error_ = nullptr;
-    rc = zk_host_encode(raw_.engine_, src, take, fs, raw_.level_, raw_.checksum_ ? 1 : 0, d_prefix, tail, &Encoder::sink, this);
+    const zk_cdict *cd = tail ? nullptr : raw_.cdict_;                         // an explicit prefix overrides the dictionary
+    if (cd) rc = zk_host_encode(raw_.engine_, src, take, fs, raw_.level_, raw_.checksum_ ? 1 : 0, cd->content_len ? cd->d_content : nullptr, cd->content_len,
+                                &Encoder::sink, this, cd);
+    else rc = zk_host_encode(raw_.engine_, src, take, fs, raw_.level_, raw_.checksum_ ? 1 : 0, d_prefix, tail, &Encoder::sink, this);
     if (sink_error_) std::rethrow_exception(sink_error_);
     if (rc != 0) throw Error::from_engine_code(rc, zk_engine_last_hip_error(raw_.engine_));
 }
@@ -307,13 +327,13 @@ size_t Encoder::speculate_compressed(const uint8_t *buf, size_t len, const uint8
         size_t k = (len - pos) / s - 2;                                        // the tail (two frames' worth or more) is not speculated on
         if (raw_.ratio_ <= 0 && pos == 0) k = std::min<size_t>(k, 4);          // no ratio yet: a small first batch measures it
         k = std::min<size_t>(k, 8192);
-        spec_out_.resize((size_t)zk_compress_bound((uint64_t)k * s, (uint32_t)s));
+        spec_out_.resize((size_t)host_bound(raw_.cdict_, (uint64_t)k * s, (uint32_t)s));
         spec_c_.resize(k); spec_d_.resize(k);
         uint32_t nf = 0;
         uint64_t written = 0;
-        const int rc = zk_encode_frames_prefix(raw_.engine_, buf + pos, (uint64_t)k * s, (uint32_t)s, raw_.level_, raw_.checksum_ ? 1 : 0,
-                                               prefix, prefix ? prefix_len : 0, spec_out_.data(), spec_out_.size(), spec_c_.data(), spec_d_.data(),
-                                               (uint32_t)k, &nf, &written);
+        const int rc = encode_host_frames(raw_.engine_, raw_.cdict_, buf + pos, (uint64_t)k * s, (uint32_t)s, raw_.level_, raw_.checksum_ ? 1 : 0,
+                                          prefix, prefix ? prefix_len : 0, spec_out_.data(), spec_out_.size(), spec_c_.data(), spec_d_.data(),
+                                          (uint32_t)k, &nf, &written);
         if (rc != 0) throw Error::from_engine_code(rc, zk_engine_last_hip_error(raw_.engine_));
         size_t at = 0, good = 0;
         uint64_t sum_c = 0;
@@ -429,6 +449,12 @@ size_t Encoder::compress_with_prefix(const uint8_t *buf, size_t len, const uint8
     // the last full frame stays open (upstream closes it on the NEXT call), so it is held back
     if (batch_len_ > (size_t)fs * batch_frames_) submit_batch(false);
     return total_len;
+}
+
+bool Encoder::set_dictionary(const zk_cdict *cdict)
+{
+    if (batch_len_ || since_end_) return false;               // frames gathered, or a frame open since the last end_frame
+    return raw_.set_dictionary(cdict);
 }
 
 size_t Encoder::end_frame()                                                    // encode.rs:704-717

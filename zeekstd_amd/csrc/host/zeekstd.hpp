@@ -16,6 +16,7 @@
 #include <vector>
 
 struct zk_engine;
+struct zk_cdict;
 
 namespace zeekstd {
 
@@ -342,6 +343,10 @@ public:
     SeekTable into_seek_table() { return std::move(seek_table_); }                   // :492
     void reset_frame();                                                              // :501-507
     void reset_seek_table() { seek_table_ = SeekTable(); }                           // :524
+    // engine-specific (ZSTD_CCtx_loadDictionary on the context behind with_cctx, :142-155): frames that begin without an explicit prefix
+    // are encoded against the compiled dictionary (zk_encode_frames_dict); nullptr = none.  Allowed while no frame is open and nothing is
+    // buffered: false (stage_wrong) otherwise, and nothing changes.  The zk_cdict must outlive the encoder's use of it.
+    bool set_dictionary(const struct zk_cdict *cdict);
 
 private:
     friend class Encoder;
@@ -369,6 +374,7 @@ private:
     std::vector<uint8_t> piece_out_;
     const uint8_t *frame_prefix_ = nullptr;   // prefix referenced when the frame in progress began (encode.rs:334-338)
     size_t frame_prefix_len_ = 0;
+    const struct zk_cdict *cdict_ = nullptr;  // set_dictionary: what frames without a prefix are encoded against
 };
 
 class Encoder {                                                                      // encode.rs:570-800
@@ -388,6 +394,7 @@ public:
     uint64_t finish_format(Format format);                                           // :755-775
     size_t write(const uint8_t *buf, size_t len) { return compress(buf, len); }      // impl io::Write, :791-794
     void flush();                                                                    // :796-799
+    bool set_dictionary(const struct zk_cdict *cdict);   // RawEncoder::set_dictionary for the frames this encoder cuts: nothing gathered, no frame open
 
 private:
     void submit_batch(bool include_partial);

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include "zk_device.h"
 #include "zk_enc_device.h"
+#include "zk_enc_dict.h"
 #include "zk_kernels.h"
 
 // ------------------------------------------------------------------------------------------------ match + parse
@@ -129,8 +130,11 @@ struct ZkeBitsL {
 // the FSE states -- so that the writers can start with the kernel:
 //   seqs[i]  <- extra bits of LL | ML | OF back to back (<= 16 + 15 + 26 with long-distance offsets), their count << 58
 //   mpos[i]  <- LL code | ML code << 8 | OF code << 16
-__global__ __launch_bounds__(1024) void zk_k_enc_fse_build(const ZkEncFrame *frames, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
-                                                          const ZkEncTables *predef, ZkEncTables *ftab, uint32_t min_seq)
+// DICT (zk_encode_frames_dict* with a formatted dictionary; zk_enc_dict.h has the rules): every frame with sequences is measured, and per
+// table the cheapest of predefined / own / the dictionary's is taken; bit 8 + t of ZkEncTables::custom says "table t is the dictionary's".
+template <bool DICT>
+__device__ __forceinline__ void zke_fse_build_body(const ZkEncFrame *frames, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
+                                                   const ZkEncTables *predef, ZkEncTables *ftab, uint32_t min_seq, const ZkEncDictDev *dd)
 {
     __shared__ uint32_t s_llv[36], s_mlv[56];              // base | extra bits << 24 (the same in every frame)
     __shared__ uint32_t h[3][64];
@@ -187,6 +191,7 @@ __global__ __launch_bounds__(1024) void zk_k_enc_fse_build(const ZkEncFrame *fra
     // the predefined set is the starting point (value tables, and whatever stays predefined)
     for (uint32_t i = tid; i < sizeof(ZkEncTables) / 4; i += 1024) ((uint32_t *)T)[i] = ((const uint32_t *)predef)[i];
     __syncthreads();
+    if constexpr (!DICT) {
     if (tid < 3 && s_nseq >= min_seq) {
         const int t = (int)tid;
         const int nsym = t == 0 ? 36 : t == 1 ? 32 : 53, L = zke_fse_log(t, s_nseq);
@@ -204,6 +209,65 @@ __global__ __launch_bounds__(1024) void zk_k_enc_fse_build(const ZkEncFrame *fra
             }
         }
     }
+    } else {
+        // the counted codes' cost under the predefined and under the dictionary's tables: a lane per table and code (what one lane
+        // per table would read code after code out of HBM)
+        __shared__ uint32_t s_pick[3], s_lacks[3];
+        __shared__ unsigned long long s_sum[2][3];
+        if (tid < 3) { s_lacks[tid] = 0; s_sum[0][tid] = 0; s_sum[1][tid] = 0; }
+        __syncthreads();
+        if (tid < 192 && h[tid >> 6][tid & 63]) {
+            const uint32_t t = tid >> 6, s = tid & 63, n = h[t][s], cp = dd->cost_predef[t][s], cd = dd->cost[t][s];
+            if (cp != ZKE_COST_NONE) atomicAdd(&s_sum[0][t], (unsigned long long)n * cp);
+            if (cd == ZKE_COST_NONE) s_lacks[t] = 1; else atomicAdd(&s_sum[1][t], (unsigned long long)n * cd);
+        }
+        __syncthreads();
+        if (tid < 3) {
+            const int t = (int)tid;
+            const int nsym = t == 0 ? 36 : t == 1 ? 32 : 53, L = zke_fse_log(t, s_nseq);
+            int pick = ZKE_PICK_PREDEF;
+            if (s_nseq) {
+                // (the frame's own table is described into the frame's set; it stays unused unless picked)
+                uint32_t d = 0;
+                pick = zke_dict_choose_sums(h[t], t, s_nseq, fr.n_blocks, min_seq, s_sum[0][t], !s_lacks[t], s_sum[1][t], dd->T.al[t], norm[t], T->desc[t], &d, nullptr);
+                if (pick == ZKE_PICK_OWN) {
+                    uint16_t *st = t == 0 ? T->ll_state : t == 1 ? T->of_state : T->ml_state;
+                    uint32_t *dfs = t == 0 ? T->ll_dfs : t == 1 ? T->of_dfs : T->ml_dfs;
+                    uint32_t *dnb = t == 0 ? T->ll_dnb : t == 1 ? T->of_dnb : T->ml_dnb;
+                    zke_build_ctable(norm[t], nsym, L, st, dfs, dnb, sym[t], cumul[t]);
+                    T->al[t] = (uint32_t)L; T->dlen[t] = d;
+                    atomicOr(&T->custom, 1u << t);
+                }
+            }
+            s_pick[t] = (uint32_t)pick;
+        }
+        __syncthreads();
+        // the dictionary's tables where they were picked: copied by all lanes
+        const ZkEncTables &D = dd->T;
+        if (s_pick[0] == ZKE_PICK_DICT) {
+            for (uint32_t i = tid; i < 512; i += 1024) T->ll_state[i] = D.ll_state[i];
+            if (tid < 36) { T->ll_dfs[tid] = D.ll_dfs[tid]; T->ll_dnb[tid] = D.ll_dnb[tid]; }
+        }
+        if (s_pick[1] == ZKE_PICK_DICT) {
+            for (uint32_t i = tid; i < 256; i += 1024) T->of_state[i] = D.of_state[i];
+            if (tid < 32) { T->of_dfs[tid] = D.of_dfs[tid]; T->of_dnb[tid] = D.of_dnb[tid]; }
+        }
+        if (s_pick[2] == ZKE_PICK_DICT) {
+            for (uint32_t i = tid; i < 512; i += 1024) T->ml_state[i] = D.ml_state[i];
+            if (tid < 56) { T->ml_dfs[tid] = D.ml_dfs[tid]; T->ml_dnb[tid] = D.ml_dnb[tid]; }
+        }
+        if (tid < 3 && s_pick[tid] == ZKE_PICK_DICT) { T->al[tid] = D.al[tid]; T->dlen[tid] = 0; atomicOr(&T->custom, 0x100u << tid); }
+    }
+}
+__global__ __launch_bounds__(1024) void zk_k_enc_fse_build(const ZkEncFrame *frames, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
+                                                          const ZkEncTables *predef, ZkEncTables *ftab, uint32_t min_seq)
+{
+    zke_fse_build_body<false>(frames, blocks, seqs, mpos, predef, ftab, min_seq, nullptr);
+}
+__global__ __launch_bounds__(1024) void zk_k_enc_fse_build_dict(const ZkEncFrame *frames, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
+                                                               const ZkEncTables *predef, ZkEncTables *ftab, uint32_t min_seq, const ZkEncDictDev *dd)
+{
+    zke_fse_build_body<true>(frames, blocks, seqs, mpos, predef, ftab, min_seq, dd);
 }
 
 #ifndef ZKE_ENT_WAVES
@@ -689,19 +753,93 @@ __global__ __launch_bounds__(ZKE_ENT_THREADS) void zk_k_enc_entropy(const uint8_
     ZKE_ECLK_END();
 }
 
+// ------------------------------------------------------------------------------------------------ dictionary route: the first block's literals
+// zk_k_enc_entropy itself has no dictionary variant: its code, LDS and registers are those of the other routes.  What the dictionary adds to
+// the literals runs behind it, one wave per frame, in front of zk_k_enc_sizes: would the literals of the frame's first block be smaller as
+// a Treeless_Literals_Block under the dictionary's tree than what the entropy stage made of them (own tree, raw or RLE)?  Decided on the bytes
+// both produce (zke_treeless_size: the code lengths summed per stream).  Where they are, the streams are written into the block's stream
+// area (<= 11 bits per literal: they fit where 4 x (q + q / 2 + 16) bytes were reserved) and the literals head is replaced.  Later blocks
+// are not looked at: an own tree may have replaced the dictionary's by then.  A first block the entropy stage stored raw or as RLE stays
+// as it is (its pieces were not kept).
+__global__ __launch_bounds__(256) void zk_k_enc_dict_lits(const ZkEncFrame *frames, uint32_t nframes, ZkEncBlock *blocks, const uint8_t *lits, uint8_t *scratch,
+                                                          const ZkEncDictDev *dd)
+{
+    const uint32_t lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= nframes) return;
+    const ZkEncFrame fr = frames[f];
+    if (!fr.n_blocks) return;
+    ZkEncBlock *blk = &blocks[fr.block_base];
+    const uint32_t nlit = blk->nlit;
+    if (blk->mode != 2 || nlit == 0) return;
+    uint8_t *small = scratch + blk->scratch_base, *head = small + sizeof(ZkEncPieces);
+    ZkEncPieces pc; memcpy(&pc, small, sizeof pc);
+    const uint8_t *lt = lits + blk->lit_base;
+    const bool single = nlit < 256;
+    const uint32_t q = (nlit + 3) / 4, scap = q + (q >> 1) + 16;
+    // legality and the streams' bits
+    uint64_t bits[4] = {0, 0, 0, 0};
+    uint32_t bad = 0;
+    for (uint32_t i = lane; i < nlit; i += 64) {
+        const uint32_t l = dd->huf_len[lt[i]], k = single ? 0 : i / q;
+        bad |= l == 0;
+        bits[0] += k == 0 ? l : 0; bits[1] += k == 1 ? l : 0; bits[2] += k == 2 ? l : 0; bits[3] += k == 3 ? l : 0;
+    }
+    if (__ballot(bad)) return;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1)
+#pragma unroll
+        for (int k = 0; k < 4; k++) bits[k] += (uint64_t)__shfl_xor((unsigned long long)bits[k], m, 64);
+    uint32_t z[4];
+    const uint32_t new_sz = zke_treeless_size(nlit, bits, z);
+    const uint32_t old_sz = pc.head_lit + (pc.lit_mode == 2 ? (uint32_t)pc.z[0] + pc.z[1] + pc.z[2] + pc.z[3] : pc.lit_mode == 0 ? nlit : 0u);
+    if (!new_sz || new_sz >= old_sz) return;
+    if (single ? z[0] > 4 * scap : (z[0] > scap || z[1] > scap || z[2] > scap || z[3] > scap)) return;   // (cannot happen: 11 bits per literal at most)
+    const uint32_t total = new_sz + pc.head_seq + pc.zs;
+    // the streams: lane k writes stream k, last literal first, bits LSB first, the end mark behind them
+    uint8_t *stemp = small + ZKE_SMALL;
+    if (lane < (single ? 1u : 4u)) {
+        const uint32_t k = lane, n_k = single ? nlit : k < 3 ? q : nlit - 3 * q;
+        const uint8_t *sp = lt + k * q;
+        uint8_t *o = stemp + k * scap;
+        uint64_t acc = 0; uint32_t n = 0, at = 0;
+        for (uint32_t i = n_k; i-- > 0;) {
+            const uint32_t sy = sp[i];
+            acc |= (uint64_t)dd->huf_code[sy] << n; n += dd->huf_len[sy];
+            while (n >= 8) { o[at++] = (uint8_t)acc; acc >>= 8; n -= 8; }
+        }
+        acc |= 1ull << n; n++;
+        while (n > 0) { o[at++] = (uint8_t)acc; acc >>= 8; n = n > 8 ? n - 8 : 0; }
+    }
+    if (lane == 0) {
+        uint8_t seqhead[8];
+        for (uint32_t i = 0; i < pc.head_seq; i++) seqhead[i] = head[pc.head_lit + i];
+        const uint32_t comp = new_sz - (nlit < 1024 ? 3 : nlit < 16384 ? 4 : 5);
+        uint32_t w = zke_treeless_header(head, nlit, comp);
+        if (!single) for (int k = 0; k < 3; k++) { head[w++] = (uint8_t)z[k]; head[w++] = (uint8_t)(z[k] >> 8); }
+        for (uint32_t i = 0; i < pc.head_seq; i++) head[w + i] = seqhead[i];
+        for (int k = 0; k < 4; k++) pc.z[k] = (uint16_t)z[k];
+        pc.head_lit = (uint8_t)w; pc.lit_mode = 2;
+        memcpy(small, &pc, sizeof pc);
+        blk->csize = total;
+        blk->modes_off = new_sz + pc.head_seq - 1;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ frame sizes, scan, assemble
-__global__ __launch_bounds__(64) void zk_k_enc_sizes(const ZkEncFrame *frames, uint32_t nframes, ZkEncBlock *blocks, const ZkEncTables *ftab, int checksum,
-                                                     uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes)
+// DICT: the header carries did.width bytes of Dictionary_ID; tables that are the dictionary's (custom bits 8..10) need no defining block
+template <bool DICT>
+__device__ __forceinline__ void zke_sizes_body(const ZkEncFrame *frames, uint32_t nframes, ZkEncBlock *blocks, const ZkEncTables *ftab, int checksum,
+                                               uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes, ZkEncDictId did)
 {
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nframes) return;
     const ZkEncFrame fr = frames[f];
     uint64_t c;
-    if (fr.d_size == 0) c = 9;                                      // 28 B5 2F FD 20 00 01 00 00
+    if (fr.d_size == 0) c = 9 + (DICT ? did.width : 0u);            // 28 B5 2F FD 20 00 01 00 00
     else {
-        c = 6;
+        c = 6 + (DICT ? did.width : 0u);
         // the frame's first compressed block with sequences defines its tables: it grows by the descriptions
-        bool defined = ftab[f].custom == 0;
+        bool defined = (DICT ? ftab[f].custom & 7u : ftab[f].custom) == 0;
         for (uint32_t b = 0; b < fr.n_blocks; b++) {
             ZkEncBlock &blk = blocks[fr.block_base + b];
             if (!defined && blk.mode == 2 && blk.nseq) {
@@ -717,6 +855,16 @@ __global__ __launch_bounds__(64) void zk_k_enc_sizes(const ZkEncFrame *frames, u
     c_size64[f] = c;
     if (c_sizes) c_sizes[f] = (uint32_t)c;
     if (d_sizes) d_sizes[f] = fr.d_size;
+}
+__global__ __launch_bounds__(64) void zk_k_enc_sizes(const ZkEncFrame *frames, uint32_t nframes, ZkEncBlock *blocks, const ZkEncTables *ftab, int checksum,
+                                                     uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes)
+{
+    zke_sizes_body<false>(frames, nframes, blocks, ftab, checksum, c_size64, c_sizes, d_sizes, ZkEncDictId{0, 0});
+}
+__global__ __launch_bounds__(64) void zk_k_enc_sizes_dict(const ZkEncFrame *frames, uint32_t nframes, ZkEncBlock *blocks, const ZkEncTables *ftab, int checksum,
+                                                          uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes, ZkEncDictId did)
+{
+    zke_sizes_body<true>(frames, nframes, blocks, ftab, checksum, c_size64, c_sizes, d_sizes, did);
 }
 
 // exclusive scan of n u64 values (one workgroup); out[n] = total
@@ -830,6 +978,35 @@ __global__ __launch_bounds__(256) void zk_k_enc_assemble(const uint8_t *src, con
         for (int k = 0; k < 5; k++) { const uint32_t t = (len[k] & ~15u) + (tid & 15); if ((tid >> 4) == (uint32_t)k && t < len[k]) o[to[k] + t] = from[k][t]; }
     }
 }
+// The dictionary route: zk_k_enc_assemble itself is the other routes' (zk_k_enc_sizes_dict left did.width bytes of room behind the six header
+// bytes it writes, so every block already lies where it belongs); this pass behind it names the dictionary and its tables.
+// Threads [0, nframes): the Dictionary_ID flag and field -- behind the window descriptor, or in front of an empty frame's Frame_Content_Size.
+// Threads [nframes, nframes + nblocks): Symbol_Compression_Modes of a compressed block with sequences says Repeat_Mode for the tables that
+// are the dictionary's (custom bits 8..10; the entropy stage wrote Predefined_Mode there), in a defining block as in every other.
+__global__ __launch_bounds__(256) void zk_k_enc_dict_patch(const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint32_t nblocks, const ZkEncTables *ftab,
+                                                           const uint64_t *out_off, int checksum, uint8_t *dst, ZkEncDictId did)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < nframes) {
+        uint8_t *o = dst + out_off[i];
+        const uint32_t flag = zke_dict_id_flag(did.width);
+        if (frames[i].d_size == 0) {
+            uint32_t w = 4;
+            o[w++] = (uint8_t)((checksum ? 0x24 : 0x20) | flag);
+            for (uint32_t k = 0; k < did.width; k++) o[w++] = (uint8_t)(did.id >> (8 * k));
+            o[w++] = 0x00; o[w++] = 0x01; o[w++] = 0x00; o[w++] = 0x00;
+        } else {
+            o[4] = (uint8_t)((checksum ? 0x04 : 0x00) | flag);
+            for (uint32_t k = 0; k < did.width; k++) o[6 + k] = (uint8_t)(did.id >> (8 * k));
+        }
+        return;
+    }
+    if (i - nframes >= nblocks) return;
+    const ZkEncBlock &blk = blocks[i - nframes];
+    const uint32_t dict_tabs = ftab[blk.frame].custom >> 8;
+    if (blk.mode != 2 || !blk.nseq || !dict_tabs) return;
+    dst[out_off[blk.frame] + blk.out_at + 3 + blk.modes_off] |= (uint8_t)zke_modes_byte(dict_tabs, 3);
+}
 
 // ------------------------------------------------------------------------------------------------ launchers
 void zk_launch_enc_stage_hist(hipStream_t st, const uint8_t *src, const uint8_t *prefix_tail, const ZkEncFrame *frames, uint32_t nframes, uint8_t *stage)
@@ -882,20 +1059,23 @@ void zk_launch_enc_match(hipStream_t st, const uint8_t *src, const ZkEncFrame *s
 #undef ZKE_GO
 }
 void zk_launch_enc_fse_build(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
-                             const ZkEncTables *predef, ZkEncTables *ftab)
+                             const ZkEncTables *predef, ZkEncTables *ftab, const ZkEncDictDev *dd)
 {
     (void)src;
+    if (dd) { hipLaunchKernelGGL(zk_k_enc_fse_build_dict, dim3(nframes), dim3(1024), 0, st, frames, blocks, seqs, mpos, predef, ftab, ZKE_FSE_MIN_SEQ, dd); return; }
     hipLaunchKernelGGL(zk_k_enc_fse_build, dim3(nframes), dim3(1024), 0, st, frames, blocks, seqs, mpos, predef, ftab, ZKE_FSE_MIN_SEQ);
 }
 void zk_launch_enc_entropy(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, ZkEncBlock *blocks, uint32_t nblocks,
-                           uint64_t *seqs, uint32_t *mpos, const uint8_t *lits, uint8_t *scratch, const ZkEncTables *ftab)
+                           uint64_t *seqs, uint32_t *mpos, const uint8_t *lits, uint8_t *scratch, const ZkEncTables *ftab, uint32_t nframes, const ZkEncDictDev *dd)
 {
     if (!nblocks) return;
     hipLaunchKernelGGL(zk_k_enc_entropy, dim3((nblocks + ZKE_ENT_BLOCKS - 1) / ZKE_ENT_BLOCKS), dim3(ZKE_ENT_THREADS), sizeof(ZkeEntShared), st, src, frames, blocks, nblocks, seqs, mpos, lits, scratch, ftab);
+    if (dd) hipLaunchKernelGGL(zk_k_enc_dict_lits, dim3((nframes + 3) / 4), dim3(256), 0, st, frames, nframes, blocks, lits, scratch, dd);
 }
 void zk_launch_enc_sizes(hipStream_t st, const ZkEncFrame *frames, uint32_t nframes, ZkEncBlock *blocks, const ZkEncTables *ftab, int checksum,
-                         uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes)
+                         uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes, const ZkEncDictId *did)
 {
+    if (did) { hipLaunchKernelGGL(zk_k_enc_sizes_dict, dim3((nframes + 63) / 64), dim3(64), 0, st, frames, nframes, blocks, ftab, checksum, c_size64, c_sizes, d_sizes, *did); return; }
     hipLaunchKernelGGL(zk_k_enc_sizes, dim3((nframes + 63) / 64), dim3(64), 0, st, frames, nframes, blocks, ftab, checksum, c_size64, c_sizes, d_sizes);
 }
 void zk_launch_scan64(hipStream_t st, const uint64_t *in, uint32_t n, uint64_t *out)
@@ -903,7 +1083,8 @@ void zk_launch_scan64(hipStream_t st, const uint64_t *in, uint32_t n, uint64_t *
     hipLaunchKernelGGL(zk_k_scan64, dim3(1), dim3(1024), 0, st, in, n, out);
 }
 void zk_launch_enc_assemble(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint32_t nblocks, const ZkEncTables *ftab,
-                            const uint8_t *lits, const uint8_t *scratch, const uint64_t *out_off, const uint64_t *c_size64, const uint64_t *hashes, int checksum, uint8_t *dst)
+                            const uint8_t *lits, const uint8_t *scratch, const uint64_t *out_off, const uint64_t *c_size64, const uint64_t *hashes, int checksum, uint8_t *dst, const ZkEncDictId *did)
 {
     hipLaunchKernelGGL(zk_k_enc_assemble, dim3(nframes + nblocks), dim3(256), 0, st, src, frames, nframes, blocks, ftab, lits, scratch, out_off, c_size64, hashes, checksum, dst);
+    if (did) hipLaunchKernelGGL(zk_k_enc_dict_patch, dim3((nframes + nblocks + 255) / 256), dim3(256), 0, st, frames, nframes, blocks, nblocks, ftab, out_off, checksum, dst, *did);
 }

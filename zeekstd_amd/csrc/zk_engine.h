@@ -82,6 +82,7 @@ struct zk_engine {
         zk_devbuf dense;                    // dense far history (level 0 / >= 3, frames beyond the ring's reach): a candidate per input byte (ZkEncLdm::dense)
         zk_devbuf ldm;                      // prefix beyond the matcher's ring: the long-distance table (ZkEncLdm)
         uint64_t dense_slice_bytes = 0;     // input bytes the dense scratch is reserved for (0 = 4 GiB), ZK_CHOICE_ENC_DENSE_SLICE_KIB
+        uint64_t dict_slice_bytes = 0;      // dictionary route: bytes of [content tail | frame] records staged at a time (0 = 1 GiB), ZK_CHOICE_ENC_DICT_SLICE_KIB
         ZkEncTables tables;
         bool tables_ready = false;
         // second queue: the checksum kernel (one serial chain per frame) runs beside the entropy stage; created on first use
@@ -154,10 +155,25 @@ void zk_hostpipe_destroy(zk_engine *e);
 void zk_hostpipe_tune(zk_engine *e);                    // applies zk_engine::pipe_contexts / pipe_chunk_bytes (between calls)
 enum { ZK_HW_ENC_TOTAL = 8, ZK_HW_RANGES = 10 };   // index into zk_engine::h_words of the encoder's total-size read-back; of the three words zk_read_ranges_dev reads back
 constexpr uint64_t ZK_RANGE_PASS_DEFAULT = 1ull << 30;
+// A compiled dictionary (zk_cdict_create; zk_enc_dict.h): the device copies an encode against it reads.  It belongs to the engine it was made on.
+struct ZkEncDictDev;
+struct zk_cdict {
+    zk_engine *e = nullptr;
+    uint32_t id = 0, id_width = 0;
+    bool formatted = false;
+    void *d_content = nullptr;              // the content's last `content_len` bytes (what the matcher can reach: zke_ldm_usable) + ZKE_LDM_SLACK
+    uint64_t content_len = 0;
+    ZkEncDictDev *d_tab = nullptr;          // formatted dictionaries: the compression side of the four tables
+};
 struct zk_enc_args {
     const void *d_src; uint64_t n; uint32_t frame_size; int level, checksum;
     const void *d_prefix; uint64_t prefix_len; void *d_dst; uint64_t dst_cap; void *d_c_sizes, *d_d_sizes;
+    // the dictionary route: d_prefix / prefix_len are the dictionary's content (the caller sets them from it); the frames name cdict->id, the
+    // records are staged in slices, and with a formatted dictionary the entropy stage runs its dictionary variants
+    const zk_cdict *cdict = nullptr;
 };
+// what a destination of an encode must hold for the call never to ask: zk_compress_bound, on the dictionary route zk_compress_bound_dict
+uint64_t zk_enc_bound(const zk_enc_args &a);
 int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32_t *nf_out);
 int zk_encode_finish(zk_engine *e, hipStream_t st, uint64_t *written_out);
 
@@ -179,7 +195,7 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
 // valid during the call): the compressed bytes and the chunk's seek entries.  sink returns 0 to go on.
 typedef int (*zk_host_sink)(void *user, const uint8_t *data, uint64_t n, const uint32_t *c_sizes, const uint32_t *d_sizes, uint32_t n_frames);
 int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum, const void *d_prefix,
-                   uint64_t prefix_len, zk_host_sink sink, void *user);
+                   uint64_t prefix_len, zk_host_sink sink, void *user, const zk_cdict *cdict = nullptr);     // cdict: d_prefix / prefix_len are its content
 // Upload (or reuse) the device copy of a prefix on behalf of `owner`; returns the device pointer in *d_out.
 int zk_engine_stage_prefix(zk_engine *e, const void *owner, const uint8_t *prefix, uint64_t len, bool force, const void **d_out);
 // multi-threaded memcpy on the engine's worker threads (large host-side copies of the zeekstd:: classes)

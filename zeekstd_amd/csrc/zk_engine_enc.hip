@@ -6,6 +6,8 @@
 #include "zk_engine.h"
 #include "zk_kernels.h"
 #include "zk_enc_plan.h"
+#include "zk_enc_dict.h"
+#include "zk_dict.h"
 
 // ---------------------------------------------------------------- predefined FSE compression tables (host, once)
 void zk_build_enc_tables(ZkEncTables *t)
@@ -36,6 +38,17 @@ extern "C" uint64_t zk_compress_bound(uint64_t n, uint32_t frame_size)
     return n + nf * (6 + 4 + 3 * blocks_per_frame) + 16;
 }
 
+// The dictionary route adds the largest Dictionary_ID field to every frame and nothing else: a block is stored raw unless its compressed form
+// is smaller, a dictionary table replaces a description (the one thing that lets a block outgrow its input) and never adds one, and a
+// Treeless literals section is taken only where it is smaller than the section it replaces.
+extern "C" uint64_t zk_compress_bound_dict(uint64_t n, uint32_t frame_size)
+{
+    if (frame_size == 0) return 0;
+    const uint64_t nf = n == 0 ? 1 : (n + frame_size - 1) / frame_size;
+    return zk_compress_bound(n, frame_size) + 4 * nf;
+}
+uint64_t zk_enc_bound(const zk_enc_args &a) { return a.cdict ? zk_compress_bound_dict(a.n, a.frame_size) : zk_compress_bound(a.n, a.frame_size); }
+
 extern "C" int zk_encode_frames_dev(zk_engine *e, const void *d_src, uint64_t n, uint32_t frame_size, int level, int checksum,
                                     void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint32_t *n_frames_out,
                                     uint64_t *written_out, void *stream)
@@ -65,6 +78,11 @@ struct ZkEncLayout {
     size_t dense_span;                      // input bytes the dense scratch covers: a slice of whole frames, or all of it
     uint32_t *cand, *part, *poff;           // Enc::dense: dense_span + ZKE_DENSE_SLACK candidates, as many sorted positions, the pass offsets
     bool cks_beside;                        // the checksums run on the second queue and are joined before the assembly
+    // the dictionary route
+    uint8_t *stage;                         // the staged records of one slice (Enc::hist)
+    uint32_t stage_frames;                  // frames per slice of staged records; 0: the records are staged in one piece (zk_enc_stage_hist)
+    const ZkEncDictDev *dd;                 // a formatted dictionary's tables, or null
+    ZkEncDictId did; const ZkEncDictId *pdid;   // the Dictionary_ID field (pdid: null on every other route and for a raw-content dictionary)
 };
 template <class T> int zk_enc_reserve(zk_engine *e, zk_devbuf &b, size_t bytes, T **p)
 {
@@ -126,6 +144,10 @@ static int zk_enc_plan_upload(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
     ZK_HIP(hipMemcpyAsync(L.dtab, L.htab, sizeof(ZkEncTables), hipMemcpyHostToDevice, st));
     zk_profile_begin(e);
     L.src = L.msrc = (const uint8_t *)a.d_src;
+    L.stage = nullptr; L.stage_frames = 0;
+    L.dd = a.cdict && a.cdict->formatted ? a.cdict->d_tab : nullptr;
+    L.did = ZkEncDictId{a.cdict ? a.cdict->id : 0u, a.cdict ? a.cdict->id_width : 0u};
+    L.pdid = L.dd ? &L.did : nullptr;
     return 0;
 }
 
@@ -134,7 +156,14 @@ static int zk_enc_plan_upload(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
 static int zk_enc_stage_hist(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
     const uint32_t hist = L.pl.hist;
-    if (hist) {
+    if (hist && a.cdict) {
+        // the dictionary route: a bounded buffer for slices of whole frames, staged by zk_enc_match right before each slice is matched
+        const uint64_t rec = (uint64_t)hist + a.frame_size, cap = e->enc.dict_slice_bytes ? e->enc.dict_slice_bytes : 1ull << 30;
+        const uint64_t per = cap / rec ? cap / rec : 1;
+        L.stage_frames = (uint32_t)(per < L.pl.nf ? per : L.pl.nf);
+        int rc;
+        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)(L.stage_frames * rec) + 64, &L.stage))) return rc;
+    } else if (hist) {
         uint8_t *stage;
         int rc;
         if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)L.pl.nf * ((size_t)hist + a.frame_size) + 64, &stage))) return rc;
@@ -195,8 +224,8 @@ static int zk_enc_far_history(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
 static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
     const uint32_t nf = L.pl.nf, nseg = L.pl.nseg, frame_size = a.frame_size;
-    const bool sliced = L.ldm.dense && L.dense_span < a.n;
-    const uint32_t fpf = sliced ? (uint32_t)(L.dense_span / frame_size) : nf, spf = (frame_size + ZKE_SEGMENT - 1) / ZKE_SEGMENT;   // frames per slice, segments per whole frame
+    const bool sliced = (L.ldm.dense && L.dense_span < a.n) || (L.stage_frames && L.stage_frames < nf);     // (never both: a prefix has no dense history)
+    const uint32_t fpf = L.stage_frames ? L.stage_frames : sliced ? (uint32_t)(L.dense_span / frame_size) : nf, spf = (frame_size + ZKE_SEGMENT - 1) / ZKE_SEGMENT;   // frames per slice, segments per whole frame
     zk_kernel_timer whole(e, ZK_K_ENC_MATCH, st, sliced);
     for (uint32_t f0 = 0; f0 < nf; f0 += fpf) {
         const uint32_t f1 = nf - f0 < fpf ? nf : f0 + fpf, s0 = f0 * spf, s1 = f1 == nf ? nseg : f1 * spf;
@@ -208,6 +237,12 @@ static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipS
             zk_launch_enc_dense_cand(st, L.src, L.d_segs + s0, s1 - s0, sl, L.cand - lo, L.part - lo, L.poff);
         }
         zk_kernel_timer t(e, ZK_K_ENC_MATCH, st, !sliced);
+        if (L.stage_frames) {
+            // the slice's [content tail | frame] records: the frames' m_off count from the call's first record, so the buffer is handed on
+            // shifted by the slice's first record (the next slice's staging runs behind this slice's matcher on the same queue)
+            L.msrc = L.stage - (uint64_t)f0 * ((uint64_t)L.pl.hist + frame_size);
+            zk_launch_enc_stage_hist(st, L.src, (const uint8_t *)a.d_prefix + (a.prefix_len - L.pl.hist), L.d_frames + f0, f1 - f0, (uint8_t *)L.msrc);
+        }
         zk_launch_enc_match(st, L.msrc, L.d_segs + s0, s1 - s0, L.d_blocks, L.seqs, L.lits, a.level, sl);
     }
     return 0;
@@ -217,7 +252,7 @@ static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipS
 static int zk_enc_table_build(zk_engine *e, const zk_enc_args &, ZkEncLayout &L, hipStream_t st)
 {
     zk_kernel_timer t(e, ZK_K_ENC_FSE_BUILD, st);
-    zk_launch_enc_fse_build(st, L.src, L.d_frames, L.pl.nf, L.d_blocks, L.seqs, L.mpos, L.dtab, L.ftab);
+    zk_launch_enc_fse_build(st, L.src, L.d_frames, L.pl.nf, L.d_blocks, L.seqs, L.mpos, L.dtab, L.ftab, L.dd);
     return 0;
 }
 
@@ -245,7 +280,7 @@ static int zk_enc_checksums_fork(zk_engine *e, const zk_enc_args &a, ZkEncLayout
 static int zk_enc_entropy(zk_engine *e, const zk_enc_args &, ZkEncLayout &L, hipStream_t st)
 {
     zk_kernel_timer t(e, ZK_K_ENC_ENTROPY, st);
-    zk_launch_enc_entropy(st, L.src, L.d_frames, L.d_blocks, L.pl.nb, L.seqs, L.mpos, L.lits, L.scratch, L.ftab);
+    zk_launch_enc_entropy(st, L.src, L.d_frames, L.d_blocks, L.pl.nb, L.seqs, L.mpos, L.lits, L.scratch, L.ftab, L.pl.nf, L.dd);
     return 0;
 }
 
@@ -253,7 +288,7 @@ static int zk_enc_entropy(zk_engine *e, const zk_enc_args &, ZkEncLayout &L, hip
 static int zk_enc_sizes_total(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
     const uint32_t nf = L.pl.nf;
-    zk_launch_enc_sizes(st, L.d_frames, nf, L.d_blocks, L.ftab, a.checksum, L.c64, (uint32_t *)a.d_c_sizes, (uint32_t *)a.d_d_sizes);
+    zk_launch_enc_sizes(st, L.d_frames, nf, L.d_blocks, L.ftab, a.checksum, L.c64, (uint32_t *)a.d_c_sizes, (uint32_t *)a.d_d_sizes, L.pdid);
     zk_launch_scan64(st, L.c64, nf, L.out_off);
     ZK_HIP(hipMemcpyAsync(e->h_words + ZK_HW_ENC_TOTAL, L.out_off + nf, 8, hipMemcpyDeviceToHost, st));
     return 0;
@@ -262,7 +297,7 @@ static int zk_enc_sizes_total(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
 // a destination below the bound: the frames may not fit, and the total decides before anything is written
 static int zk_enc_fit_check(zk_engine *e, const zk_enc_args &a, ZkEncLayout &, hipStream_t st)
 {
-    if (a.dst_cap >= zk_compress_bound(a.n, a.frame_size)) return 0;
+    if (a.dst_cap >= zk_enc_bound(a)) return 0;
     ZK_HIP(hipStreamSynchronize(st));
     return e->h_words[ZK_HW_ENC_TOTAL] > a.dst_cap ? -(int)ZK_E_DST_TOO_SMALL : 0;
 }
@@ -272,7 +307,7 @@ static int zk_enc_assemble(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, h
 {
     if (L.cks_beside) ZK_HIP(hipStreamWaitEvent(st, e->enc.ev_join, 0));
     zk_kernel_timer t(e, ZK_K_ENC_COMPACT, st);
-    zk_launch_enc_assemble(st, L.src, L.d_frames, L.pl.nf, L.d_blocks, L.pl.nb, L.ftab, L.lits, L.scratch, L.out_off, L.c64, L.hashes, a.checksum, (uint8_t *)a.d_dst);
+    zk_launch_enc_assemble(st, L.src, L.d_frames, L.pl.nf, L.d_blocks, L.pl.nb, L.ftab, L.lits, L.scratch, L.out_off, L.c64, L.hashes, a.checksum, (uint8_t *)a.d_dst, L.pdid);
     return 0;
 }
 
@@ -317,6 +352,64 @@ extern "C" int zk_encode_frames_prefix_dev(zk_engine *e, const void *d_src, uint
     if (!e) return ZK_ERR_ARGUMENT;
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     zk_enc_args a{d_src, n, frame_size, level, checksum, d_prefix, prefix_len, d_dst, dst_cap, d_c_sizes, d_d_sizes};
+    uint32_t nf = 0;
+    int rc = zk_encode_enqueue(e, a, st, &nf);
+    if (rc) return rc;
+    uint64_t total = 0;
+    if ((rc = zk_encode_finish(e, st, &total))) return rc;
+    if (n_frames_out) *n_frames_out = nf;
+    if (written_out) *written_out = total;
+    return 0;
+}
+
+// ---------------------------------------------------------------- the dictionary route (zk_enc_dict.h)
+extern "C" int zk_cdict_create(zk_engine *e, const zk_dict *d, zk_cdict **out)
+{
+    if (!e || !d || !out) return ZK_ERR_ARGUMENT;
+    *out = nullptr;
+    ZK_HIP(hipSetDevice(e->device));
+    zk_cdict *c = new zk_cdict();
+    c->e = e; c->formatted = d->L.formatted; c->id = d->L.id; c->id_width = zke_dict_id_width(d->L.id);
+    const uint8_t *content = d->bytes.data() + d->L.content_off;
+    const uint64_t clen = d->bytes.size() - d->L.content_off;
+    // what the matcher can reach of the content: its ring's window and, beyond it, the long-distance table's span
+    c->content_len = zke_ldm_usable(clen);
+    auto fail = [&](int rc) { zk_cdict_free(c); return rc; };
+    if (hipMalloc(&c->d_content, (size_t)c->content_len + ZKE_LDM_SLACK) != hipSuccess) { (void)hipGetLastError(); e->last_err = "hipMalloc (dictionary content)"; return fail(ZK_ERR_HIP); }
+    if (hipMemset(c->d_content, 0, (size_t)c->content_len + ZKE_LDM_SLACK) != hipSuccess ||
+        (c->content_len && hipMemcpy(c->d_content, content + (clen - c->content_len), c->content_len, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipGetLastError(); e->last_err = "hipMemcpy (dictionary content)"; return fail(ZK_ERR_HIP);
+    }
+    if (c->formatted) {
+        if (!e->enc.tables_ready) { zk_build_enc_tables(&e->enc.tables); e->enc.tables_ready = true; }
+        ZkEncDictDev *h = new ZkEncDictDev;
+        const uint32_t r = zke_dict_build(d->bytes.data(), d->L, e->enc.tables, h);
+        hipError_t he = r ? hipSuccess : hipMalloc((void **)&c->d_tab, sizeof(ZkEncDictDev));
+        if (!r && he == hipSuccess) he = hipMemcpy(c->d_tab, h, sizeof(ZkEncDictDev), hipMemcpyHostToDevice);
+        delete h;
+        if (r) return fail(-(int)r);
+        if (he != hipSuccess) { (void)hipGetLastError(); e->last_err = "hipMalloc / hipMemcpy (dictionary tables)"; return fail(ZK_ERR_HIP); }
+    }
+    *out = c;
+    return 0;
+}
+extern "C" void zk_cdict_free(zk_cdict *c)
+{
+    if (!c) return;
+    if (c->e) (void)hipSetDevice(c->e->device);
+    if (c->d_content) (void)hipFree(c->d_content);
+    if (c->d_tab) (void)hipFree(c->d_tab);
+    delete c;
+}
+extern "C" uint32_t zk_cdict_id(const zk_cdict *c) { return c ? c->id : 0; }
+
+extern "C" int zk_encode_frames_dict_dev(zk_engine *e, const void *d_src, uint64_t n, uint32_t frame_size, int level, int checksum, const zk_cdict *cdict,
+                                         void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint32_t *n_frames_out, uint64_t *written_out, void *stream)
+{
+    if (!e || !cdict || cdict->e != e) return ZK_ERR_ARGUMENT;
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    // a dictionary without content (a formatted one may have none) leaves nothing to stage: the frames still name it and may use its tables
+    zk_enc_args a{d_src, n, frame_size, level, checksum, cdict->content_len ? cdict->d_content : nullptr, cdict->content_len, d_dst, dst_cap, d_c_sizes, d_d_sizes, cdict};
     uint32_t nf = 0;
     int rc = zk_encode_enqueue(e, a, st, &nf);
     if (rc) return rc;

@@ -719,7 +719,7 @@ extern "C" int zk_decode_frames_prefix(zk_engine *e, const uint8_t *comp, uint64
 
 // ---------------------------------------------------------------------------------------------- encode
 int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum, const void *d_prefix,
-                   uint64_t prefix_len, zk_host_sink sink, void *user)
+                   uint64_t prefix_len, zk_host_sink sink, void *user, const zk_cdict *cdict)
 {
     if (!e || frame_size == 0 || frame_size > ZK_SEEKABLE_MAX_FRAME_SIZE || !sink || (n && !src)) return ZK_ERR_ARGUMENT;
     const uint64_t nf64 = n == 0 ? 1 : (n + frame_size - 1) / frame_size;
@@ -742,7 +742,7 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
     const bool small = nchunks == 1 && n <= (4u << 20);
     if (!small) { if ((rc = zk_hostpipe_rings(e, hp))) return rc; }                 // the compressed bytes travel back through the ring
     const uint64_t max_in = per * frame_size < n ? per * frame_size : n;
-    const uint64_t max_bound = zk_compress_bound(max_in, frame_size);
+    const uint64_t max_bound = cdict ? zk_compress_bound_dict(max_in, frame_size) : zk_compress_bound(max_in, frame_size);
     if (small) { if ((rc = zk_pin_reserve(e, hp->pin_small, hp->pin_small_cap, (size_t)max_in + (size_t)max_bound + 256))) return rc; }
     if ((rc = zk_pin_reserve(e, hp->pin_meta, hp->pin_meta_cap, (size_t)per * 8 * 2 + 64))) return rc;     // (c, d) sizes of two chunks
     ZkRegWindow wsrc;                                       // (after every allocation that can fail: its pool tasks point at this frame)
@@ -768,13 +768,14 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
         uint64_t f0, nf, b0, bn; chunk_range(i, f0, nf, b0, bn);
         zk_hostpipe::Slot &s = hp->es[i & 1];
         int r0;
-        if ((r0 = zk_devbuf_reserve(e, s.out, (size_t)zk_compress_bound(bn, frame_size) + 64))) return r0;      // the chunk two back has been handed to the sink by now
+        zk_enc_args a{s.in.p, bn, frame_size, level, checksum, d_prefix, d_prefix ? prefix_len : 0, s.out.p, 0, nullptr, nullptr, cdict};
+        a.dst_cap = zk_enc_bound(a);
+        if ((r0 = zk_devbuf_reserve(e, s.out, (size_t)a.dst_cap + 64))) return r0;      // the chunk two back has been handed to the sink by now
         if ((r0 = zk_devbuf_reserve(e, s.meta, (size_t)nf * 8 + 64))) return r0;
         ZK_HIP(hipStreamWaitEvent(st, s.ev_in, 0));
         if (s.out_pending) ZK_HIP(hipStreamWaitEvent(st, s.ev_out, 0));       // the chunk two back has left `out`
         uint32_t *dc = (uint32_t *)s.meta.p, *dd = dc + nf;
-        zk_enc_args a{s.in.p, bn, frame_size, level, checksum, d_prefix, d_prefix ? prefix_len : 0, s.out.p,
-                      zk_compress_bound(bn, frame_size), dc, dd};
+        a.d_dst = s.out.p; a.d_c_sizes = dc; a.d_d_sizes = dd;
         uint32_t nfo = 0;
         zk_profiling_off quiet(e, nchunks > 1);
         int r = zk_encode_enqueue(e, a, st, &nfo);
@@ -912,5 +913,23 @@ extern "C" int zk_xxh64_frames(zk_engine *e, const uint8_t *data, const uint64_t
     rc = zk_xxh64_frames_dev(e, e->st_dst.p, e->st_off.p, count, e->st_misc.p, st);
     if (rc) return rc;
     ZK_HIP(hipMemcpy(out, e->st_misc.p, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the dictionary route through the host pipeline: the content is on the device already (zk_cdict_create)
+extern "C" int zk_encode_frames_dict(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum, const zk_cdict *cdict,
+                                     uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint32_t frames_cap, uint32_t *n_frames_out,
+                                     uint64_t *written_out)
+{
+    if (!e || !cdict || cdict->e != e || frame_size == 0 || !dst || (n && !src)) return ZK_ERR_ARGUMENT;
+    const uint64_t nf = n == 0 ? 1 : (n + frame_size - 1) / frame_size;
+    if (nf > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
+    if ((c_sizes || d_sizes) && frames_cap < nf) return ZK_ERR_ARGUMENT;
+    ZkBufSink s{e, dst, dst_cap, 0, c_sizes, d_sizes, 0, false};
+    const int rc = zk_host_encode(e, src, n, frame_size, level, checksum, cdict->content_len ? cdict->d_content : nullptr, cdict->content_len, zk_buf_sink, &s, cdict);
+    if (s.overflow) return -(int)ZK_E_DST_TOO_SMALL;
+    if (rc) return rc;
+    if (n_frames_out) *n_frames_out = s.nf;
+    if (written_out) *written_out = s.pos;
     return 0;
 }

@@ -51,6 +51,7 @@ void zk_launch_small_publish(hipStream_t st, const ZkFrameInfo *infos, const uin
 
 // ---- encoder (zk_encode.hip)
 #include "zk_enc_device.h"
+struct ZkEncDictDev; struct ZkEncDictId;                // zk_enc_dict.h; a null pointer = the launch of every route without a formatted dictionary
 void zk_launch_enc_stage_hist(hipStream_t st, const uint8_t *src, const uint8_t *prefix_tail, const ZkEncFrame *frames, uint32_t nframes, uint8_t *stage);
 void zk_launch_enc_match(hipStream_t st, const uint8_t *src, const ZkEncFrame *segs, uint32_t nsegs, ZkEncBlock *blocks, uint64_t *seqs, uint8_t *lits, int level, const ZkEncLdm &ldm);
 int zk_launch_enc_ldm_build(hipStream_t st, const ZkEncLdm &ldm, uint32_t *table);                        // 0, or -1: the table could not be cleared
@@ -58,14 +59,16 @@ int zk_launch_enc_ldm_build(hipStream_t st, const ZkEncLdm &ldm, uint32_t *table
 void zk_launch_enc_dense_cand(hipStream_t st, const uint8_t *src, const ZkEncFrame *segs, uint32_t nsegs, const ZkEncLdm &ldm, uint32_t *cand, uint32_t *part, uint32_t *poff);
 int zk_launch_enc_ldm_build_frames(hipStream_t st, const uint8_t *src, const ZkEncLdm &ldm, uint32_t *table, uint32_t nframes);
 void zk_launch_enc_fse_build(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
-                             const ZkEncTables *predef, ZkEncTables *ftab);
+                             const ZkEncTables *predef, ZkEncTables *ftab, const ZkEncDictDev *dd = nullptr);
 void zk_launch_enc_entropy(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, ZkEncBlock *blocks, uint32_t nblocks,
-                           uint64_t *seqs, uint32_t *mpos, const uint8_t *lits, uint8_t *scratch, const ZkEncTables *ftab);
+                           uint64_t *seqs, uint32_t *mpos, const uint8_t *lits, uint8_t *scratch, const ZkEncTables *ftab,
+                           uint32_t nframes = 0, const ZkEncDictDev *dd = nullptr);       // dd: zk_k_enc_dict_lits over the nframes frames' first blocks behind it
 void zk_launch_enc_sizes(hipStream_t st, const ZkEncFrame *frames, uint32_t nframes, ZkEncBlock *blocks, const ZkEncTables *ftab, int checksum,
-                         uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes);
+                         uint64_t *c_size64, uint32_t *c_sizes, uint32_t *d_sizes, const ZkEncDictId *did = nullptr);
 void zk_launch_scan64(hipStream_t st, const uint64_t *in, uint32_t n, uint64_t *out);
 void zk_launch_enc_assemble(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint32_t nblocks, const ZkEncTables *ftab,
-                            const uint8_t *lits, const uint8_t *scratch, const uint64_t *out_off, const uint64_t *c_size64, const uint64_t *hashes, int checksum, uint8_t *dst);
+                            const uint8_t *lits, const uint8_t *scratch, const uint64_t *out_off, const uint64_t *c_size64, const uint64_t *hashes, int checksum, uint8_t *dst,
+                            const ZkEncDictId *did = nullptr);
 
 // ---- byte-range reads (zk_ranges.hip; the per-range arithmetic: zk_ranges.h)
 struct ZkRangeArgs { const uint64_t *d_off; uint32_t n_frames; const uint64_t *offs, *lens, *dst_off; uint32_t count; void *dst; uint64_t dst_cap; };

@@ -44,6 +44,36 @@ class Dictionary:
             self._h = None
 
 
+class EncodeDictionary:
+    """A dictionary compiled for encoding on one engine (zk_cdict_create; the counterpart of ZSTD_CDict): its content and, for a formatted
+    dictionary, the compression side of its tables live on the device.  Made once, used by any number of Engine.encode_frames(dictionary=)
+    / encode_frames_dict_dev calls of that engine; it keeps the engine alive."""
+
+    def __init__(self, engine, dictionary):
+        h = C.c_void_p()
+        rc = lib.zk_cdict_create(engine._h, dictionary._h, C.byref(h))
+        if rc != 0:
+            engine._raise(rc)
+        self._h = h
+        self._engine = engine
+
+    @property
+    def id(self) -> int:
+        return int(lib.zk_cdict_id(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._engine._h:
+                lib.zk_cdict_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """Owns one GPU's scratch + stream. One thread at a time (like a libzstd context)."""
 
@@ -88,7 +118,7 @@ class Engine:
 
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
-               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15}
+               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -186,19 +216,25 @@ class Engine:
             self._raise(rc)
         return out[:out_len].tobytes(), status[:count]
 
-    def encode_frames(self, data, frame_size=0x200000, level=1, checksum=False, prefix=None):
+    def encode_frames(self, data, frame_size=0x200000, level=1, checksum=False, prefix=None, dictionary=None):
         """Returns (compressed payload bytes, [(c_size, d_size), ...]) -- one zstd frame per frame_size bytes.
-        prefix: raw-content prefix referenced at the start of every frame (patch mode)."""
+        prefix: raw-content prefix referenced at the start of every frame (patch mode).
+        dictionary: an EncodeDictionary of this engine (zk_encode_frames_dict); not together with a prefix."""
         data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
         n = int(data.size)
         nf = max(1, -(-n // frame_size))
-        cap = int(lib.zk_compress_bound(n, frame_size))
+        if dictionary is not None and prefix:
+            raise ValueError("a prefix and a dictionary exclude each other at this level")
+        cap = int(lib.zk_compress_bound_dict(n, frame_size) if dictionary is not None else lib.zk_compress_bound(n, frame_size))
         out = np.empty(cap, dtype=np.uint8)
         cs = np.zeros(nf, np.uint32)
         ds = np.zeros(nf, np.uint32)
         nfo = C.c_uint32()
         wr = C.c_uint64()
-        if prefix:
+        if dictionary is not None:
+            rc = lib.zk_encode_frames_dict(self._h, data.ctypes.data if n else None, n, frame_size, level, int(checksum), dictionary._h,
+                                           out.ctypes.data, cap, cs.ctypes.data, ds.ctypes.data, nf, C.byref(nfo), C.byref(wr))
+        elif prefix:
             pre = np.frombuffer(bytes(prefix), dtype=np.uint8)
             rc = lib.zk_encode_frames_prefix(self._h, data.ctypes.data if n else None, n, frame_size, level, int(checksum),
                                              pre.ctypes.data, pre.size, out.ctypes.data, cap, cs.ctypes.data, ds.ctypes.data, nf,
@@ -216,6 +252,19 @@ class Engine:
         rc = lib.zk_encode_frames_dev(self._h, self._ptr(d_src), n, frame_size, level, int(checksum), self._ptr(d_dst), dst_cap,
                                       self._ptr(d_c_sizes) if d_c_sizes is not None else None,
                                       self._ptr(d_d_sizes) if d_d_sizes is not None else None, C.byref(nfo), C.byref(wr), stream)
+        if rc != 0:
+            self._raise(rc)
+        return nfo.value, wr.value
+
+    def encode_frames_dict_dev(self, d_src, n, frame_size, level, checksum, dictionary, d_dst, dst_cap, d_c_sizes=None, d_d_sizes=None, stream=None):
+        """zk_encode_frames_dict_dev: device tensors in and out, `dictionary` an EncodeDictionary of this engine (None is refused by the
+        library).  Returns (frames, bytes written)."""
+        nfo = C.c_uint32()
+        wr = C.c_uint64()
+        rc = lib.zk_encode_frames_dict_dev(self._h, self._ptr(d_src), n, frame_size, level, int(checksum),
+                                           dictionary._h if dictionary is not None else None, self._ptr(d_dst), dst_cap,
+                                           self._ptr(d_c_sizes) if d_c_sizes is not None else None,
+                                           self._ptr(d_d_sizes) if d_d_sizes is not None else None, C.byref(nfo), C.byref(wr), stream)
         if rc != 0:
             self._raise(rc)
         return nfo.value, wr.value
