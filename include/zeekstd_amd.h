@@ -112,9 +112,12 @@ enum {
     ZK_CHOICE_ENC_DENSE_SLICE_KIB = 15, /* encodes with dense far history (level 0 / >= 3, frames beyond the matcher's ring): input KiB whose candidate scratch
                                         * (8 bytes per input byte) is reserved at a time (1..2^22; 0 = 2^22, 4 GiB).  A longer input is matched slice after
                                         * slice of whole frames over that scratch, never less than one frame; the bytes produced do not depend on it */
-    ZK_CHOICE_ENC_DICT_SLICE_KIB = 16  /* zk_encode_frames_dict*: KiB of [dictionary content | frame] records staged for the matcher at a time (1..2^22;
+    ZK_CHOICE_ENC_DICT_SLICE_KIB = 16, /* zk_encode_frames_dict*: KiB of [dictionary content | frame] records staged for the matcher at a time (1..2^22;
                                         * 0 = 2^20, 1 GiB).  A longer input is staged and matched slice after slice of whole frames over that buffer, never
                                         * less than one frame; the bytes produced do not depend on it */
+    ZK_CHOICE_ENC_PLAN = 17            /* zk_encode_frame_list_dev: where the frame / block / segment records are made: 0 = by the number of frames,
+                                        * 1 = on the host (written and uploaded, 160 bytes per frame), 2 = on the device from the offsets.  The same
+                                        * records, so the same bytes */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -304,6 +307,7 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *   zk_encode_frames[_prefix][_dev], zk_raw_encoder_*, zk_encoder_*                 served    served    served     (scratch of their own)
  *   zk_cdict_create / _free / _id, zk_encode_frames_dict[_dev],                     served    served    served     (the same; a zk_cdict is no decode state)
  *     zk_raw_encoder_set_dictionary, zk_encoder_set_dictionary
+ *   zk_encode_frame_list[_dev]                                                      served    served    served     (the encoder's scratch, as the rows above)
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
  *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
@@ -406,6 +410,30 @@ int zk_encode_frames_dict_dev(zk_engine *e, const void *d_src, uint64_t n, uint3
 int zk_encode_frames_dict(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum, const zk_cdict *cdict,
                           uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint32_t frames_cap, uint32_t *n_frames,
                           uint64_t *written);
+
+/* ---- Frames of caller-given sizes: one frame per record, log line, row or tensor, or an archive re-encoded on its own frame boundaries.
+ * off[count + 1]: non-decreasing uint64 prefix sums -- the array the decode calls later take as d_off.  Frame i is src[off[i], off[i + 1]); off[0]
+ * need not be 0.  A size of 0 makes the empty frame that n == 0 makes on the other routes.  count == 0 returns 0, sets *written = 0 and writes
+ * nothing.  cdict == NULL and prefix_len == 0: the plain route; a non-empty prefix: the prefix route (zk_encode_frames_prefix*); cdict: the
+ * dictionary route (zk_encode_frames_dict*); a cdict together with a non-empty prefix is ZK_ERR_ARGUMENT.  So is a decreasing list and a frame above
+ * ZK_SEEKABLE_MAX_FRAME_SIZE; count > ZK_SEEKABLE_MAX_FRAMES is ZK_ERR_FRAME_INDEX_TOO_LARGE, decided before the list is read.  A refused call
+ * writes nothing.
+ * Frame i is byte for byte the frame zk_encode_frames[_prefix|_dict]_dev makes of those bytes alone -- n = size_i, frame_size = max(size_i, 1), the
+ * same level, checksum flag, prefix and cdict -- at every level: window, block cut, in-frame far history, dense history, long-distance table into a
+ * long prefix, dictionary tables, Treeless first block.  A list of equal sizes gives exactly the output of zk_encode_frames*.
+ * c_sizes / d_sizes (may be NULL): count entries each.  *written: the sum of the c_sizes.
+ * dst_cap >= zk_compress_bound_list(n, count, with_dictionary) = n + 3 * (n / 1024) + (53 + (with_dictionary ? 4 : 0)) * count, n = off[count] -
+ * off[0], always suffices: it is an upper bound of the sum of the frames' own bounds.  Below it, -70 and "destination untouched" are as for
+ * zk_encode_frames_dev.
+ * The device entry point synchronises its stream ONCE AT THE START: the offsets (8 bytes per frame) come to the host, which checks them, and
+ * with them the totals of the plan when the device makes it (ZK_CHOICE_ENC_PLAN: from 1000 frames on unless pinned).  d_off is device memory.  The host-pointer call runs through the host pipeline in groups of whole frames. */
+uint64_t zk_compress_bound_list(uint64_t n, uint32_t count, int with_dictionary);
+int zk_encode_frame_list_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, int checksum,
+                             const void *d_prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                             void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint64_t *written, void *stream);
+int zk_encode_frame_list(zk_engine *e, const uint8_t *src, const uint64_t *off, uint32_t count, int level, int checksum,
+                         const uint8_t *prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                         uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint64_t *written);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside

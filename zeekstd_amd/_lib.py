@@ -82,6 +82,11 @@ _sig = {
                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "zk_encode_frames_dict_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_int, _P, _P, C.c_uint64, _P, _P,
                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
+    "zk_compress_bound_list": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int]),
+    "zk_encode_frame_list_dev": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P,
+                                           C.POINTER(C.c_uint64), _P]),
+    "zk_encode_frame_list": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P,
+                                       C.POINTER(C.c_uint64)]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

@@ -105,7 +105,33 @@ struct ZkEncLdm {
     // prefixes, frames within the ring's reach).
     const uint32_t *dense;
     uint32_t dlog, pad2;
+    // IN-FRAME far history under a caller-given FRAME LIST (zk_encode_frame_list*): frame_size / n_total say nothing then.  lf: the nlf frames
+    // that qualify (zke_ldm_in_frame), by ascending start, each with its size and where its 2^zke_ldm_log(size) entries begin in `table`; the
+    // first zke_ldm_list_shared() entries of `table` stay empty and serve every other frame (within the ring's reach: no entry could be taken).  nullptr: no list.
+    const struct ZkEncLdmFrame *lf;
+    uint32_t nlf, pad3;
 };
+struct ZkEncLdmFrame {
+    uint64_t start;             // the frame's src_off
+    uint64_t tbase;             // first entry of its table
+    uint32_t size, pad;
+};
+ZK_HD uint32_t zke_ldm_list_shared() { return 1u << zke_ldm_log(ZKE_WINDOW); }      // entries of the empty table: what the largest frame without its own addresses
+// The list route's frame of a segment that starts its frame at src_off: its entry of lf, or null for a frame that does not qualify.  Only
+// frames with bytes have segments, and no two of those start at one offset, so the start names the frame even among empty frames around it.
+ZK_HD const ZkEncLdmFrame *zke_ldm_list_frame(const ZkEncLdm &ldm, uint64_t src_off)
+{
+    uint32_t lo = 0, hi = ldm.nlf;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (ldm.lf[mid].start < src_off) lo = mid + 1; else hi = mid; }
+    return lo < ldm.nlf && ldm.lf[lo].start == src_off ? &ldm.lf[lo] : nullptr;
+}
+// bytes of the frame a segment record belongs to: the list's, or the uniform cut's.  (A frame off the list's table is one segment: its size.)
+ZK_HD uint32_t zke_ldm_frame_bytes(const ZkEncLdm &ldm, const ZkEncFrame &sg)
+{
+    if (ldm.lf) { const ZkEncLdmFrame *q = zke_ldm_list_frame(ldm, sg.src_off); return q ? q->size : sg.seg_at + sg.d_size; }
+    const uint64_t left = ldm.n_total - sg.src_off;
+    return (uint32_t)(left < ldm.frame_size ? left : ldm.frame_size);
+}
 constexpr uint32_t ZKE_DENSE_AHEAD = 4, ZKE_DENSE_BONUS = 3;
 constexpr uint32_t ZKE_DENSE_PASSES_MAX = 32;          // passes of the candidate kernel at 2^18 slots (2^13 of both tables in LDS per pass)
 constexpr uint32_t ZKE_DENSE_MIN = 6, ZKE_DENSE_MARGIN = 2, ZKE_DENSE_NONE = 0xFFFFFFFFu, ZKE_DENSE_SLACK = 4096 + 16;

@@ -41,14 +41,15 @@ __global__ __launch_bounds__(256) void zk_k_enc_ldm_build(ZkEncLdm ldm, uint32_t
     }
 }
 // The same for the frames' own tables (in-frame far history): blockIdx.y = frame; frame f's table = table + (f << ldm.log), of which
-// its own 2^zke_ldm_log(size) entries are used.
+// its own 2^zke_ldm_log(size) entries are used.  Under a frame list (ZkEncLdm::lf) blockIdx.y counts the frames that have a table.
 __global__ __launch_bounds__(256) void zk_k_enc_ldm_build_frames(const uint8_t *src, ZkEncLdm ldm, uint32_t *table, uint32_t f0)
 {
-    const uint64_t f = (uint64_t)f0 + blockIdx.y, at = f * ldm.frame_size;
-    const uint64_t n = ldm.n_total - at < ldm.frame_size ? ldm.n_total - at : ldm.frame_size;
+    // (under a frame list: the f-th frame that qualifies, its table where the list says)
+    const uint64_t f = (uint64_t)f0 + blockIdx.y, at = ldm.lf ? ldm.lf[f].start : f * ldm.frame_size;
+    const uint64_t n = ldm.lf ? ldm.lf[f].size : ldm.n_total - at < ldm.frame_size ? ldm.n_total - at : ldm.frame_size;
     const uint32_t log = zke_ldm_log(n);
     const uint8_t *s = src + at;
-    uint32_t *t = table + (f << ldm.log);
+    uint32_t *t = table + (ldm.lf ? ldm.lf[f].tbase : f << ldm.log);
     for (uint64_t i = 4ull * ((uint64_t)blockIdx.x * 256 + threadIdx.x); i + ZKE_LDM_MIN <= n; i += 4ull * gridDim.x * 256) {
         uint32_t w[5];
         for (int k = 0; k < 5; k++) { w[k] = 0; const uint64_t q = i + 4 * k; if (q + 4 <= n) memcpy(&w[k], s + q, 4); else for (uint64_t b = q; b < n; b++) w[k] |= (uint32_t)s[b] << (8 * (b - q)); }
@@ -114,8 +115,7 @@ __global__ __launch_bounds__(1024) void zk_k_enc_dense_part(const uint8_t *src, 
     __shared__ uint32_t total[ZKD_NBMAX], start[ZKD_NBMAX + 1];
     const ZkEncFrame sg = segs[blockIdx.x];
     const uint8_t *frame = src + sg.src_off;
-    const uint64_t left = ldm.n_total - sg.src_off;
-    const uint32_t fsz = (uint32_t)(left < ldm.frame_size ? left : ldm.frame_size);
+    const uint32_t fsz = zke_ldm_frame_bytes(ldm, sg);
     const uint32_t s0 = sg.seg_at, e1 = s0 + sg.d_size, tid = threadIdx.x, dlog = ldm.dlog, wave = tid >> 6, nb = 1u << (dlog - ZKD_PLOG);
     uint32_t *lst = part + sg.src_off + s0;                         // the segment's lists, pass after pass
     static_assert(16 * ZKD_NBMAX <= 1024, "one counter per lane");
@@ -153,8 +153,7 @@ __global__ __launch_bounds__(1024) void zk_k_enc_dense_cand(const uint8_t *src, 
     const uint32_t nwg = gridDim.x, seg = (nwg & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (nwg >> 3) + (blockIdx.x >> 3);
     const ZkEncFrame sg = segs[seg];
     const uint8_t *frame = src + sg.src_off;
-    const uint64_t left = ldm.n_total - sg.src_off;
-    const uint32_t fsz = (uint32_t)(left < ldm.frame_size ? left : ldm.frame_size);
+    const uint32_t fsz = zke_ldm_frame_bytes(ldm, sg);
     const uint32_t s0 = sg.seg_at, e1 = s0 + sg.d_size, tid = threadIdx.x, dlog = ldm.dlog;
     uint32_t *out = cand + sg.src_off;                              // indexed by the position inside the frame
     const uint32_t *olist = part + sg.src_off + s0, *plist = olist - ZKE_SEGMENT;           // the segment before mine is a whole one, and the one before me in the list

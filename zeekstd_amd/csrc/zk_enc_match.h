@@ -193,9 +193,11 @@ __global__ __launch_bounds__(ZKE_THREADS) void zk_k_enc_match(const uint8_t *src
     const uint64_t abs0 = !LDM ? 0 : ldm.inframe ? fr.seg_at - hist : ldm.plen + fr.seg_at - hist;
     ZkEncLdm LD = ldm;
     if (LDM && ldm.inframe) {
-        const uint64_t fsz = ldm.n_total - fr.src_off < ldm.frame_size ? ldm.n_total - fr.src_off : ldm.frame_size;
+        // (under a frame list the frame's size and table come from the list; a frame without an entry there reads the shared empty table)
+        const ZkEncLdmFrame *lq = ldm.lf ? zke_ldm_list_frame(ldm, fr.src_off) : nullptr;
+        const uint64_t fsz = ldm.lf ? (lq ? lq->size : fr.seg_at + fr.d_size) : ldm.n_total - fr.src_off < ldm.frame_size ? ldm.n_total - fr.src_off : ldm.frame_size;
         LD.pfx = base - abs0; LD.plen = fsz; LD.u0 = 0; LD.log = zke_ldm_log(fsz);
-        LD.table = ldm.table + ((fr.src_off / ldm.frame_size) << ldm.log);
+        LD.table = ldm.lf ? ldm.table + (lq ? lq->tbase : 0) : ldm.table + ((fr.src_off / ldm.frame_size) << ldm.log);
     }
     // dense far history (round 6): per position of my segment its far candidate, length | catch-up << 5 | distance << 8, as zk_k_enc_dense_cand left it
     // (0: none); four positions per lane and group in one 16-byte read

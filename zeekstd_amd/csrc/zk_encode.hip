@@ -43,6 +43,7 @@ extern "C" void zk_debug_enc_clocks(unsigned long long *out, int reset)
 #include "zk_enc_match.h"
 #include "zk_enc_match2.h"
 #include "zk_enc_far.h"
+#include "zk_enc_plan_dev.h"
 #ifdef ZKE_ENT_CLOCKS
 // experiments: the same for the entropy kernel (per wave: slot = 4 * phase + wave; tools/ent_clocks.py)
 __device__ unsigned long long zke_dbg_clk[48];
@@ -1013,6 +1014,16 @@ void zk_launch_enc_stage_hist(hipStream_t st, const uint8_t *src, const uint8_t 
 {
     hipLaunchKernelGGL(zk_k_enc_stage_hist, dim3(nframes), dim3(256), 0, st, src, prefix_tail, frames, stage);
 }
+// the plan of a frame list on the device (zk_enc_plan_dev.h): the running sums (sums[count] = the totals), then the records
+void zk_launch_enc_plan_scan(hipStream_t st, const uint64_t *d_off, uint32_t count, bool prefix, ZkEncPlanSum *sums)
+{
+    hipLaunchKernelGGL(zk_k_enc_plan_scan, dim3(1), dim3(ZKP_SCAN_THREADS), 0, st, d_off, count, prefix ? 1u : 0u, sums);
+}
+void zk_launch_enc_plan_fill(hipStream_t st, const uint64_t *d_off, uint32_t count, int level, uint64_t prefix_len, uint32_t hist, const ZkEncPlanSum *sums,
+                             ZkEncFrame *frames, ZkEncBlock *blocks, ZkEncFrame *segs, uint64_t *doff)
+{
+    hipLaunchKernelGGL(zk_k_enc_plan_fill, dim3((count + 255) / 256), dim3(256), 0, st, d_off, count, level, prefix_len, hist, sums, frames, blocks, segs, doff);
+}
 void zk_launch_enc_dense_cand(hipStream_t st, const uint8_t *src, const ZkEncFrame *segs, uint32_t nsegs, const ZkEncLdm &ldm, uint32_t *cand, uint32_t *part, uint32_t *poff)
 {
     if (!nsegs) return;
@@ -1021,10 +1032,11 @@ void zk_launch_enc_dense_cand(hipStream_t st, const uint8_t *src, const ZkEncFra
 }
 // (both return the HIP verdict of clearing the table: a table that was not cleared holds an earlier call's positions, and the matcher
 //  would follow them -- ADVICE r4 / r5)
-int zk_launch_enc_ldm_build_frames(hipStream_t st, const uint8_t *src, const ZkEncLdm &ldm, uint32_t *table, uint32_t nframes)
+// (a frame list: nframes = the frames with a table, ldm.lf; list_entries = all their entries + the shared empty ones, list_max = the largest such frame)
+int zk_launch_enc_ldm_build_frames(hipStream_t st, const uint8_t *src, const ZkEncLdm &ldm, uint32_t *table, uint32_t nframes, uint64_t list_entries, uint32_t list_max)
 {
-    if (hipMemsetAsync(table, 0xFF, ((size_t)nframes * sizeof(uint32_t)) << ldm.log, st) != hipSuccess) return -1;
-    const uint64_t wgs = ((uint64_t)ldm.frame_size + 4095) / 4096;
+    if (hipMemsetAsync(table, 0xFF, ldm.lf ? (size_t)list_entries * sizeof(uint32_t) : ((size_t)nframes * sizeof(uint32_t)) << ldm.log, st) != hipSuccess) return -1;
+    const uint64_t wgs = ((uint64_t)(ldm.lf ? list_max : ldm.frame_size) + 4095) / 4096;
     // a grid's y dimension ends at 65535 (4 GiB of 64 KiB frames are 65536 of them): frames in launches of at most that many
     for (uint32_t f0 = 0; f0 < nframes; f0 += 65535u) {
         const uint32_t cnt = nframes - f0 < 65535u ? nframes - f0 : 65535u;

@@ -77,10 +77,14 @@ struct zk_engine {
         zk_devbuf words;                    // per frame: c_size64, out_off, hashes, d_off; behind them the predefined tables
         zk_devbuf ftab;                     // the frames' tables
         uint8_t *pin = nullptr; size_t pin_cap = 0;   // pinned host copy of the frame / block lists of the encode in flight
+        uint8_t *pin_off = nullptr; size_t pin_off_cap = 0;   // zk_encode_frame_list_dev: the caller's offsets, brought to the host
+        uint8_t *pin_lf = nullptr; size_t pin_lf_cap = 0;     // ... and, under a frame list with in-frame far history, of the records of the frames that have a table (ZkEncLdmFrame)
         zk_devbuf hist;                     // prefix mode: [prefix tail | frame] records for the matcher
         zk_devbuf seg;                      // frames above ZKE_SEGMENT: the matcher's segment records
         zk_devbuf dense;                    // dense far history (level 0 / >= 3, frames beyond the ring's reach): a candidate per input byte (ZkEncLdm::dense)
         zk_devbuf ldm;                      // prefix beyond the matcher's ring: the long-distance table (ZkEncLdm)
+        zk_devbuf plan;                     // a frame list planned on the device: the frames' running sums (ZkEncPlanSum, zk_enc_plan_dev.h)
+        int plan_choice = 0;                // ZK_CHOICE_ENC_PLAN
         uint64_t dense_slice_bytes = 0;     // input bytes the dense scratch is reserved for (0 = 4 GiB), ZK_CHOICE_ENC_DENSE_SLICE_KIB
         uint64_t dict_slice_bytes = 0;      // dictionary route: bytes of [content tail | frame] records staged at a time (0 = 1 GiB), ZK_CHOICE_ENC_DICT_SLICE_KIB
         ZkEncTables tables;
@@ -153,7 +157,7 @@ zk_seek_table *zk_seek_table_from_cpp(const zeekstd::SeekTable *t);
 int zk_hostpipe_create(zk_engine *e);
 void zk_hostpipe_destroy(zk_engine *e);
 void zk_hostpipe_tune(zk_engine *e);                    // applies zk_engine::pipe_contexts / pipe_chunk_bytes (between calls)
-enum { ZK_HW_ENC_TOTAL = 8, ZK_HW_RANGES = 10 };   // index into zk_engine::h_words of the encoder's total-size read-back; of the three words zk_read_ranges_dev reads back
+enum { ZK_HW_ENC_TOTAL = 8, ZK_HW_RANGES = 10, ZK_HW_ENC_PLAN = 13 };   // index into zk_engine::h_words of the encoder's total-size read-back; of the three words zk_read_ranges_dev reads back; of the three words of a device plan's totals (ZkEncPlanSum)
 constexpr uint64_t ZK_RANGE_PASS_DEFAULT = 1ull << 30;
 // A compiled dictionary (zk_cdict_create; zk_enc_dict.h): the device copies an encode against it reads.  It belongs to the engine it was made on.
 struct ZkEncDictDev;
@@ -171,7 +175,16 @@ struct zk_enc_args {
     // the dictionary route: d_prefix / prefix_len are the dictionary's content (the caller sets them from it); the frames name cdict->id, the
     // records are staged in slices, and with a formatted dictionary the entropy stage runs its dictionary variants
     const zk_cdict *cdict = nullptr;
+    // a caller-given frame list (zk_encode_frame_list*): list[list_count + 1] non-decreasing prefix sums in HOST memory, checked by the entry
+    // point; frame i is d_src[list[i] - list[0], list[i + 1] - list[0]), n = list[list_count] - list[0], and frame_size is the largest frame
+    // (at least 1).  nullptr: frames of frame_size bytes.
+    const uint64_t *list = nullptr; uint32_t list_count = 0;
+    // ... planned on the device (zk_enc_plan_dev.h): the caller's offsets there, the frames' running sums (zk_k_enc_plan_scan has run) and, on the
+    // host, the totals behind them; all null: the host plans
+    const uint64_t *d_list = nullptr; const struct ZkEncPlanSum *d_plan_sums = nullptr, *plan_totals = nullptr;
 };
+// the entry points' check of a frame list (ZK_ERR_ARGUMENT / ZK_ERR_FRAME_INDEX_TOO_LARGE); *max_frame: the largest frame
+int zk_enc_list_check(const uint64_t *off, uint32_t count, uint64_t *max_frame);
 // what a destination of an encode must hold for the call never to ask: zk_compress_bound, on the dictionary route zk_compress_bound_dict
 uint64_t zk_enc_bound(const zk_enc_args &a);
 int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32_t *nf_out);
@@ -195,7 +208,8 @@ int zk_host_decode(zk_engine *e, const zk_host_src &src, const uint64_t *c_off, 
 // valid during the call): the compressed bytes and the chunk's seek entries.  sink returns 0 to go on.
 typedef int (*zk_host_sink)(void *user, const uint8_t *data, uint64_t n, const uint32_t *c_sizes, const uint32_t *d_sizes, uint32_t n_frames);
 int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum, const void *d_prefix,
-                   uint64_t prefix_len, zk_host_sink sink, void *user, const zk_cdict *cdict = nullptr);     // cdict: d_prefix / prefix_len are its content
+                   uint64_t prefix_len, zk_host_sink sink, void *user, const zk_cdict *cdict = nullptr,      // cdict: d_prefix / prefix_len are its content
+                   const uint64_t *list = nullptr, uint32_t list_count = 0);                                // a frame list (zk_enc_args::list): src is its first byte, frame_size its largest frame
 // Upload (or reuse) the device copy of a prefix on behalf of `owner`; returns the device pointer in *d_out.
 int zk_engine_stage_prefix(zk_engine *e, const void *owner, const uint8_t *prefix, uint64_t len, bool force, const void **d_out);
 // multi-threaded memcpy on the engine's worker threads (large host-side copies of the zeekstd:: classes)

@@ -61,7 +61,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     if (!e) return ZK_ERR_ARGUMENT;
     ZkKernelChoice &k = e->choice;
     switch (what) {
-    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; e->range_pass_bytes = 0; e->enc.dense_slice_bytes = 0; e->enc.dict_slice_bytes = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
+    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; e->range_pass_bytes = 0; e->enc.dense_slice_bytes = 0; e->enc.dict_slice_bytes = 0; e->enc.plan_choice = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
     case ZK_CHOICE_FSE_OWN: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; k.fse_own = value; return 0;
     case ZK_CHOICE_FSE_SHARED: if (value < 0 || value > 3) return ZK_ERR_ARGUMENT; k.fse_shared = value; return 0;
     case ZK_CHOICE_EXEC_LANES: if (value != 0 && value != 128 && value != 256 && value != 512 && value != 1024) return ZK_ERR_ARGUMENT; k.exec_lanes = value; return 0;
@@ -78,6 +78,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     case ZK_CHOICE_RANGE_PASS_MIB: if (value < 0 || value > (1 << 20)) return ZK_ERR_ARGUMENT; e->range_pass_bytes = (uint64_t)value << 20; return 0;
     case ZK_CHOICE_ENC_DENSE_SLICE_KIB: if (value < 0 || value > (1 << 22)) return ZK_ERR_ARGUMENT; e->enc.dense_slice_bytes = (uint64_t)value << 10; return 0;
     case ZK_CHOICE_ENC_DICT_SLICE_KIB: if (value < 0 || value > (1 << 22)) return ZK_ERR_ARGUMENT; e->enc.dict_slice_bytes = (uint64_t)value << 10; return 0;
+    case ZK_CHOICE_ENC_PLAN: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; e->enc.plan_choice = value; return 0;
     default: return ZK_ERR_ARGUMENT;
     }
 }
@@ -166,9 +167,11 @@ extern "C" void zk_engine_destroy(zk_engine *e)
     (void)hipStreamSynchronize(e->stream);
     zk_hostpipe_destroy(e);
     if (e->enc.pin) (void)hipHostFree(e->enc.pin);
+    if (e->enc.pin_lf) (void)hipHostFree(e->enc.pin_lf);
+    if (e->enc.pin_off) (void)hipHostFree(e->enc.pin_off);
     for (auto &c : e->dctx) if (c.st) (void)hipStreamSynchronize(c.st);
     zk_devbuf *bufs[] = {&e->dict.buf, &e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc, &e->rf_entries, &e->rf_frames,
-                         &e->enc.lists, &e->enc.seqs, &e->enc.lits, &e->enc.scratch, &e->enc.words, &e->enc.ftab, &e->enc.hist, &e->enc.seg, &e->enc.ldm, &e->enc.dense};
+                         &e->enc.lists, &e->enc.seqs, &e->enc.lits, &e->enc.scratch, &e->enc.words, &e->enc.ftab, &e->enc.hist, &e->enc.seg, &e->enc.ldm, &e->enc.dense, &e->enc.plan};
     for (zk_devbuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (e->h_words) (void)hipHostFree(e->h_words);
     for (int k = 0; k < ZK_NKERNELS; k++) { if (e->ev_start[k]) (void)hipEventDestroy(e->ev_start[k]); if (e->ev_stop[k]) (void)hipEventDestroy(e->ev_stop[k]); }

@@ -47,7 +47,27 @@ extern "C" uint64_t zk_compress_bound_dict(uint64_t n, uint32_t frame_size)
     const uint64_t nf = n == 0 ? 1 : (n + frame_size - 1) / frame_size;
     return zk_compress_bound(n, frame_size) + 4 * nf;
 }
-uint64_t zk_enc_bound(const zk_enc_args &a) { return a.cdict ? zk_compress_bound_dict(a.n, a.frame_size) : zk_compress_bound(a.n, a.frame_size); }
+// A frame list: the sum of the frames' own bounds, zk_compress_bound(s, max(s, 1)) (+ 4 with a dictionary) = s + 3 * ceil(max(s, 1) / 1024) + 50 (+ 4),
+// from above: every ceil is at most s / 1024 + 1, and the sum of the floors at most n / 1024.
+extern "C" uint64_t zk_compress_bound_list(uint64_t n, uint32_t count, int with_dictionary)
+{
+    return n + 3 * (n / 1024) + (uint64_t)(53 + (with_dictionary ? 4 : 0)) * count;
+}
+uint64_t zk_enc_bound(const zk_enc_args &a)
+{
+    if (a.list) return zk_compress_bound_list(a.n, a.list_count, a.cdict != nullptr);
+    return a.cdict ? zk_compress_bound_dict(a.n, a.frame_size) : zk_compress_bound(a.n, a.frame_size);
+}
+int zk_enc_list_check(const uint64_t *off, uint32_t count, uint64_t *max_frame)
+{
+    uint64_t mx = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] > ZK_SEEKABLE_MAX_FRAME_SIZE) return ZK_ERR_ARGUMENT;
+        if (off[i + 1] - off[i] > mx) mx = off[i + 1] - off[i];
+    }
+    *max_frame = mx;
+    return 0;
+}
 
 extern "C" int zk_encode_frames_dev(zk_engine *e, const void *d_src, uint64_t n, uint32_t frame_size, int level, int checksum,
                                     void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint32_t *n_frames_out,
@@ -76,14 +96,29 @@ struct ZkEncLayout {
     const uint8_t *src, *msrc;              // the input; what the matcher reads (prefix mode: the staged [prefix tail | frame] records)
     ZkEncLdm ldm;                           // far history of this call (zk_enc_far_history)
     size_t dense_span;                      // input bytes the dense scratch covers: a slice of whole frames, or all of it
+    uint64_t rec_total;                     // bytes of all the matcher's records: the input, in prefix mode with a history before every frame
+    uint64_t slice_cap;                     // zk_enc_match's slices of whole frames: at most this many bytes each (never less than a frame); 0: one slice
     uint32_t *cand, *part, *poff;           // Enc::dense: dense_span + ZKE_DENSE_SLACK candidates, as many sorted positions, the pass offsets
     bool cks_beside;                        // the checksums run on the second queue and are joined before the assembly
     // the dictionary route
     uint8_t *stage;                         // the staged records of one slice (Enc::hist)
-    uint32_t stage_frames;                  // frames per slice of staged records; 0: the records are staged in one piece (zk_enc_stage_hist)
     const ZkEncDictDev *dd;                 // a formatted dictionary's tables, or null
     ZkEncDictId did; const ZkEncDictId *pdid;   // the Dictionary_ID field (pdid: null on every other route and for a raw-content dictionary)
 };
+// where frame f starts in the source, its bytes, and where its record starts in the matcher's source -- host arithmetic from the arguments alone
+// (what zke_plan_frame is handed), so that nothing on the host reads the frame records: they may have been made on the device
+inline uint64_t zk_enc_frame_src(const zk_enc_args &a, uint32_t f) { return a.list ? a.list[f] - a.list[0] : (uint64_t)f * a.frame_size; }
+inline uint32_t zk_enc_frame_bytes(const zk_enc_args &a, uint32_t f)
+{
+    if (a.list) return (uint32_t)(a.list[f + 1] - a.list[f]);
+    const uint64_t at = (uint64_t)f * a.frame_size;
+    return (uint32_t)(a.n - at < a.frame_size ? a.n - at : a.frame_size);
+}
+inline uint64_t zk_enc_frame_rec(const zk_enc_args &a, uint32_t hist, uint32_t f)
+{
+    if (!hist) return zk_enc_frame_src(a, f);
+    return a.list ? (uint64_t)f * hist + zk_enc_frame_src(a, f) : (uint64_t)f * ((uint64_t)hist + a.frame_size);
+}
 template <class T> int zk_enc_reserve(zk_engine *e, zk_devbuf &b, size_t bytes, T **p)
 {
     const int rc = zk_devbuf_reserve(e, b, bytes);
@@ -93,7 +128,7 @@ template <class T> int zk_enc_reserve(zk_engine *e, zk_devbuf &b, size_t bytes, 
 }  // namespace
 
 // Counts come in with pl (zke_plan_count); the lists are filled in between the two halves, since the sequence and scratch totals
-// that size the device side come out of the fill.
+// that size the device side come out of the fill.  (A list planned on the device comes with all its totals: nothing is filled here.)
 static int zk_enc_layout(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L)
 {
     zk_engine::Enc &c = e->enc;
@@ -105,14 +140,22 @@ static int zk_enc_layout(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L)
     const size_t segs_bytes = ((size_t)(nseg + 1) * sizeof(ZkEncFrame) + 63) & ~(size_t)63;
     const size_t segs_at = (frames_bytes + blocks_bytes + doff_bytes + sizeof(ZkEncTables) + 63) & ~(size_t)63;
     int rc;
-    if ((rc = zk_pin_reserve(e, c.pin, c.pin_cap, frames_bytes + blocks_bytes + doff_bytes + sizeof(ZkEncTables) + 64 + segs_bytes))) return rc;
     L.frames_bytes = frames_bytes;
-    L.frames = (ZkEncFrame *)c.pin;
-    L.blocks = (ZkEncBlock *)(c.pin + frames_bytes);
-    L.doff = (uint64_t *)(c.pin + frames_bytes + blocks_bytes);
-    L.htab = (ZkEncTables *)(c.pin + frames_bytes + blocks_bytes + doff_bytes);
-    L.segs = (ZkEncFrame *)(c.pin + segs_at);
-    zke_plan_fill(a.n, a.frame_size, a.level, a.d_prefix ? a.prefix_len : 0, &pl, L.frames, L.blocks, L.segs, L.doff);
+    if (a.d_plan_sums) {
+        // planned on the device: the records exist there only (zk_enc_plan_upload launches the fill), the host holds the tables
+        if ((rc = zk_pin_reserve(e, c.pin, c.pin_cap, sizeof(ZkEncTables) + 64))) return rc;
+        L.frames = nullptr; L.blocks = nullptr; L.doff = nullptr; L.segs = nullptr;
+        L.htab = (ZkEncTables *)c.pin;
+    } else {
+        if ((rc = zk_pin_reserve(e, c.pin, c.pin_cap, frames_bytes + blocks_bytes + doff_bytes + sizeof(ZkEncTables) + 64 + segs_bytes))) return rc;
+        L.frames = (ZkEncFrame *)c.pin;
+        L.blocks = (ZkEncBlock *)(c.pin + frames_bytes);
+        L.doff = (uint64_t *)(c.pin + frames_bytes + blocks_bytes);
+        L.htab = (ZkEncTables *)(c.pin + frames_bytes + blocks_bytes + doff_bytes);
+        L.segs = (ZkEncFrame *)(c.pin + segs_at);
+        if (a.list) zke_plan_fill_list(a.list, a.level, a.d_prefix ? a.prefix_len : 0, &pl, L.frames, L.blocks, L.segs, L.doff);
+        else zke_plan_fill(a.n, a.frame_size, a.level, a.d_prefix ? a.prefix_len : 0, &pl, L.frames, L.blocks, L.segs, L.doff);
+    }
     uint8_t *lists;
     if ((rc = zk_enc_reserve(e, c.lists, frames_bytes + blocks_bytes + 256, &lists))) return rc;
     if ((rc = zk_enc_reserve(e, c.seqs, (size_t)(pl.seq_total + 1) * 12 + 64, &L.seqs))) return rc;       // packed sequences (u64) + match positions (u32)
@@ -134,17 +177,27 @@ static int zk_enc_layout(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L)
 static int zk_enc_plan_upload(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
     // the matcher sees the last `hist` bytes of the prefix right before every frame
-    if (!zke_plan_count(a.n, a.frame_size, a.d_prefix ? zke_prefix_hist(a.prefix_len) : 0, &L.pl)) return -(int)ZK_E_GENERIC;
+    const uint32_t hist = a.d_prefix ? zke_prefix_hist(a.prefix_len) : 0;
+    if (a.d_plan_sums) {
+        // a list planned on the device: the totals are here (zk_encode_frame_list_dev waited for them with the offsets)
+        const ZkEncPlanSum &t = *a.plan_totals;
+        if (t.nb > 0xFFFFFFF0u || t.nseg > 0xFFFFFFF0u) return -(int)ZK_E_GENERIC;
+        L.pl = ZkEncPlan{a.list_count, t.nb, t.nseg, hist, t.seq, t.scratch};
+    }
+    else if (!(a.list ? zke_plan_count_list(a.list, a.list_count, hist, &L.pl) : zke_plan_count(a.n, a.frame_size, hist, &L.pl))) return -(int)ZK_E_GENERIC;
     int rc;
     if ((rc = zk_enc_layout(e, a, L))) return rc;
     if (!e->enc.tables_ready) { zk_build_enc_tables(&e->enc.tables); e->enc.tables_ready = true; }
     *L.htab = e->enc.tables;
-    ZK_HIP(hipMemcpyAsync(L.d_frames, L.frames, L.frames_bytes + (size_t)L.pl.nb * sizeof(ZkEncBlock), hipMemcpyHostToDevice, st));   // frames + blocks are contiguous
-    ZK_HIP(hipMemcpyAsync(L.d_doff, L.doff, (size_t)(L.pl.nf + 1) * 8, hipMemcpyHostToDevice, st));
+    if (a.d_plan_sums) zk_launch_enc_plan_fill(st, a.d_list, a.list_count, a.level, a.d_prefix ? a.prefix_len : 0, hist, a.d_plan_sums, L.d_frames, L.d_blocks, L.d_segs, L.d_doff);
+    else {
+        ZK_HIP(hipMemcpyAsync(L.d_frames, L.frames, L.frames_bytes + (size_t)L.pl.nb * sizeof(ZkEncBlock), hipMemcpyHostToDevice, st));   // frames + blocks are contiguous
+        ZK_HIP(hipMemcpyAsync(L.d_doff, L.doff, (size_t)(L.pl.nf + 1) * 8, hipMemcpyHostToDevice, st));
+    }
     ZK_HIP(hipMemcpyAsync(L.dtab, L.htab, sizeof(ZkEncTables), hipMemcpyHostToDevice, st));
     zk_profile_begin(e);
     L.src = L.msrc = (const uint8_t *)a.d_src;
-    L.stage = nullptr; L.stage_frames = 0;
+    L.stage = nullptr; L.slice_cap = 0;
     L.dd = a.cdict && a.cdict->formatted ? a.cdict->d_tab : nullptr;
     L.did = ZkEncDictId{a.cdict ? a.cdict->id : 0u, a.cdict ? a.cdict->id_width : 0u};
     L.pdid = L.dd ? &L.did : nullptr;
@@ -156,21 +209,24 @@ static int zk_enc_plan_upload(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
 static int zk_enc_stage_hist(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
     const uint32_t hist = L.pl.hist;
+    // all the records: as many as frames, one behind the other (a list's are as long as its frames)
+    const uint64_t rec_total = a.list ? (uint64_t)L.pl.nf * hist + a.n : (uint64_t)L.pl.nf * ((uint64_t)hist + a.frame_size);
+    L.rec_total = hist ? rec_total : a.n;
     if (hist && a.cdict) {
         // the dictionary route: a bounded buffer for slices of whole frames, staged by zk_enc_match right before each slice is matched
         const uint64_t rec = (uint64_t)hist + a.frame_size, cap = e->enc.dict_slice_bytes ? e->enc.dict_slice_bytes : 1ull << 30;
-        const uint64_t per = cap / rec ? cap / rec : 1;
-        L.stage_frames = (uint32_t)(per < L.pl.nf ? per : L.pl.nf);
+        L.slice_cap = cap > rec ? cap : rec;
         int rc;
-        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)(L.stage_frames * rec) + 64, &L.stage))) return rc;
+        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)(L.slice_cap < rec_total ? L.slice_cap : rec_total) + 64, &L.stage))) return rc;
+        if (L.slice_cap >= rec_total) L.slice_cap = 0;
     } else if (hist) {
         uint8_t *stage;
         int rc;
-        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)L.pl.nf * ((size_t)hist + a.frame_size) + 64, &stage))) return rc;
+        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)rec_total + 64, &stage))) return rc;
         zk_launch_enc_stage_hist(st, L.src, (const uint8_t *)a.d_prefix + (a.prefix_len - hist), L.d_frames, L.pl.nf, stage);
         L.msrc = stage;
     }
-    ZK_HIP(hipMemcpyAsync(L.d_segs, L.segs, (size_t)L.pl.nseg * sizeof(ZkEncFrame), hipMemcpyHostToDevice, st));
+    if (L.segs) ZK_HIP(hipMemcpyAsync(L.d_segs, L.segs, (size_t)L.pl.nseg * sizeof(ZkEncFrame), hipMemcpyHostToDevice, st));
     return 0;
 }
 
@@ -180,7 +236,7 @@ static int zk_enc_far_history(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
 {
     const uint32_t frame_size = a.frame_size, nf = L.pl.nf;
     ZkEncLdm &ldm = L.ldm;
-    ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0};
+    ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0, nullptr, 0, 0};
     L.dense_span = 0;
     int rc;
     uint32_t *table;
@@ -190,8 +246,28 @@ static int zk_enc_far_history(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
     if (!L.pl.hist && zke_ldm_in_frame(a.level, plen_eff, frame_max)) {
         // in-frame far history (level >= 2, no prefix, frames beyond the ring's reach): one table per frame over its own bytes
         ldm.inframe = 1; ldm.frame_size = frame_size; ldm.n_total = a.n; ldm.log = zke_ldm_log(frame_max);
-        if ((rc = zk_enc_reserve(e, e->enc.ldm, (((size_t)nf * sizeof(uint32_t)) << ldm.log) + 64, &table))) return rc;
-        if (zk_launch_enc_ldm_build_frames(st, L.src, ldm, table, nf)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
+        if (a.list) {
+            // a table only for the frames that qualify, one behind the other after the shared empty one; their records go up in front of the tables
+            uint32_t nlf = 0;
+            for (uint32_t f = 0; f < nf; f++) nlf += zke_ldm_in_frame(a.level, plen_eff, zk_enc_frame_bytes(a, f));
+            const size_t lf_bytes = ((size_t)nlf * sizeof(ZkEncLdmFrame) + 63) & ~(size_t)63;
+            if ((rc = zk_pin_reserve(e, e->enc.pin_lf, e->enc.pin_lf_cap, lf_bytes))) return rc;
+            ZkEncLdmFrame *lf = (ZkEncLdmFrame *)e->enc.pin_lf;
+            uint64_t entries = zke_ldm_list_shared();
+            for (uint32_t f = 0, k = 0; f < nf; f++) if (zke_ldm_in_frame(a.level, plen_eff, zk_enc_frame_bytes(a, f))) {
+                lf[k++] = ZkEncLdmFrame{zk_enc_frame_src(a, f), entries, zk_enc_frame_bytes(a, f), 0};
+                entries += 1ull << zke_ldm_log(zk_enc_frame_bytes(a, f));
+            }
+            uint8_t *buf;
+            if ((rc = zk_enc_reserve(e, e->enc.ldm, lf_bytes + (size_t)entries * sizeof(uint32_t) + 64, &buf))) return rc;
+            ZK_HIP(hipMemcpyAsync(buf, lf, (size_t)nlf * sizeof(ZkEncLdmFrame), hipMemcpyHostToDevice, st));
+            table = (uint32_t *)(buf + lf_bytes);
+            ldm.lf = (const ZkEncLdmFrame *)buf; ldm.nlf = nlf;
+            if (zk_launch_enc_ldm_build_frames(st, L.src, ldm, table, nlf, entries, (uint32_t)frame_max)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
+        } else {
+            if ((rc = zk_enc_reserve(e, e->enc.ldm, (((size_t)nf * sizeof(uint32_t)) << ldm.log) + 64, &table))) return rc;
+            if (zk_launch_enc_ldm_build_frames(st, L.src, ldm, table, nf)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
+        }
         ldm.table = table;
         if (zke_dense_in_frame(a.level, plen_eff, frame_max)) {
             // dense far history (level 0 / >= 3): a far candidate per input byte, 4 bytes each (with the sorted positions 8 x the input: HBM is what this device has)
@@ -201,7 +277,9 @@ static int zk_enc_far_history(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
             // otherwise, which the tests use): the dense kernels and the match kernel run slice after slice over the same scratch, so a call
             // of any size takes at most 8 x 4 GiB of it
             const uint64_t dense_slice = e->enc.dense_slice_bytes ? e->enc.dense_slice_bytes : 4ull << 30;
-            L.dense_span = (size_t)(a.n < dense_slice ? a.n : (dense_slice / frame_size ? dense_slice / frame_size : 1) * (uint64_t)frame_size);
+            L.slice_cap = dense_slice > frame_size ? dense_slice : frame_size;
+            L.dense_span = (size_t)(a.n < L.slice_cap ? a.n : L.slice_cap);
+            if (L.slice_cap >= a.n) L.slice_cap = 0;
             if ((rc = zk_enc_reserve(e, e->enc.dense, (2 * (L.dense_span + ZKE_DENSE_SLACK) + (size_t)L.pl.nseg * (ZKE_DENSE_PASSES_MAX + 1)) * sizeof(uint32_t) + 64, &L.cand))) return rc;
             L.part = L.cand + (L.dense_span + ZKE_DENSE_SLACK); L.poff = L.part + (L.dense_span + ZKE_DENSE_SLACK);
             ldm.dense = L.cand;
@@ -223,13 +301,18 @@ static int zk_enc_far_history(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
 // of several, the whole loop as the match kernel.
 static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
-    const uint32_t nf = L.pl.nf, nseg = L.pl.nseg, frame_size = a.frame_size;
-    const bool sliced = (L.ldm.dense && L.dense_span < a.n) || (L.stage_frames && L.stage_frames < nf);     // (never both: a prefix has no dense history)
-    const uint32_t fpf = L.stage_frames ? L.stage_frames : sliced ? (uint32_t)(L.dense_span / frame_size) : nf, spf = (frame_size + ZKE_SEGMENT - 1) / ZKE_SEGMENT;   // frames per slice, segments per whole frame
+    const uint32_t nf = L.pl.nf, nseg = L.pl.nseg;
+    const bool sliced = L.slice_cap != 0;   // (dense scratch or staged records below the call's size; never both: a prefix has no dense history)
     zk_kernel_timer whole(e, ZK_K_ENC_MATCH, st, sliced);
-    for (uint32_t f0 = 0; f0 < nf; f0 += fpf) {
-        const uint32_t f1 = nf - f0 < fpf ? nf : f0 + fpf, s0 = f0 * spf, s1 = f1 == nf ? nseg : f1 * spf;
-        const uint64_t lo = (uint64_t)f0 * frame_size;
+    // where frame f's record ends in the matcher's source (without a prefix the frame's bytes in the input): what a slice is measured in
+    auto rec_end = [&](uint32_t f) { return f + 1 < nf ? zk_enc_frame_rec(a, L.pl.hist, f + 1) : L.rec_total; };
+    for (uint32_t f0 = 0, s0 = 0, f1, s1; f0 < nf; f0 = f1, s0 = s1) {
+        f1 = nf; s1 = nseg;
+        if (sliced) {
+            // whole frames while they fit, never less than one; a frame has a segment per ZKE_SEGMENT bytes
+            for (f1 = f0, s1 = s0; f1 < nf && (f1 == f0 || rec_end(f1) - zk_enc_frame_rec(a, L.pl.hist, f0) <= L.slice_cap); f1++) s1 += (zk_enc_frame_bytes(a, f1) + ZKE_SEGMENT - 1) / ZKE_SEGMENT;
+        }
+        const uint64_t lo = zk_enc_frame_src(a, f0);
         ZkEncLdm sl = L.ldm;
         if (sl.dense) {
             sl.dense = L.cand - lo;
@@ -237,10 +320,10 @@ static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipS
             zk_launch_enc_dense_cand(st, L.src, L.d_segs + s0, s1 - s0, sl, L.cand - lo, L.part - lo, L.poff);
         }
         zk_kernel_timer t(e, ZK_K_ENC_MATCH, st, !sliced);
-        if (L.stage_frames) {
+        if (L.stage) {
             // the slice's [content tail | frame] records: the frames' m_off count from the call's first record, so the buffer is handed on
             // shifted by the slice's first record (the next slice's staging runs behind this slice's matcher on the same queue)
-            L.msrc = L.stage - (uint64_t)f0 * ((uint64_t)L.pl.hist + frame_size);
+            L.msrc = L.stage - zk_enc_frame_rec(a, L.pl.hist, f0);
             zk_launch_enc_stage_hist(st, L.src, (const uint8_t *)a.d_prefix + (a.prefix_len - L.pl.hist), L.d_frames + f0, f1 - f0, (uint8_t *)L.msrc);
         }
         zk_launch_enc_match(st, L.msrc, L.d_segs + s0, s1 - s0, L.d_blocks, L.seqs, L.lits, a.level, sl);
@@ -320,7 +403,8 @@ static int zk_enc_assemble(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, h
 int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32_t *nf_out)
 {
     if (!e || a.frame_size == 0 || a.frame_size > ZK_SEEKABLE_MAX_FRAME_SIZE || !a.d_dst || (a.n && !a.d_src)) return ZK_ERR_ARGUMENT;
-    if ((a.n == 0 ? 1 : (a.n + a.frame_size - 1) / a.frame_size) > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
+    if ((a.list ? a.list_count : a.n == 0 ? 1 : (a.n + a.frame_size - 1) / a.frame_size) > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
+    if (a.list && !a.list_count) return ZK_ERR_ARGUMENT;
     ZK_HIP(hipSetDevice(e->device));
     static int (*const stages[])(zk_engine *, const zk_enc_args &, ZkEncLayout &, hipStream_t) = {
         zk_enc_plan_upload, zk_enc_stage_hist, zk_enc_far_history, zk_enc_match, zk_enc_table_build, zk_enc_checksums_fork,
@@ -416,6 +500,50 @@ extern "C" int zk_encode_frames_dict_dev(zk_engine *e, const void *d_src, uint64
     uint64_t total = 0;
     if ((rc = zk_encode_finish(e, st, &total))) return rc;
     if (n_frames_out) *n_frames_out = nf;
+    if (written_out) *written_out = total;
+    return 0;
+}
+
+// ---------------------------------------------------------------- frames of caller-given sizes
+// The offsets come to the host first (8 bytes per frame, one wait for `st`): the list is checked there, and the slices, the far-history tables
+// and -- unless the device makes it -- the plan are host arithmetic on it.  From there on it is the one pipeline above -- zk_enc_args::list --
+// on the plain, the prefix or the dictionary route.
+extern "C" int zk_encode_frame_list_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, int checksum,
+                                        const void *d_prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                                        void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint64_t *written_out, void *stream)
+{
+    if (!e || (cdict && cdict->e != e) || (cdict && d_prefix && prefix_len)) return ZK_ERR_ARGUMENT;
+    if (count > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
+    if (count == 0) { if (written_out) *written_out = 0; return 0; }
+    if (!d_off || !d_dst) return ZK_ERR_ARGUMENT;
+    ZK_HIP(hipSetDevice(e->device));
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    int rc;
+    if ((rc = zk_pin_reserve(e, e->enc.pin_off, e->enc.pin_off_cap, ((size_t)count + 1) * 8))) return rc;
+    uint64_t *off = (uint64_t *)e->enc.pin_off;
+    ZK_HIP(hipMemcpyAsync(off, d_off, ((size_t)count + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (!d_prefix) prefix_len = 0;
+    if (cdict) { d_prefix = cdict->content_len ? cdict->d_content : nullptr; prefix_len = cdict->content_len; }
+    // The plan on the device (ZK_CHOICE_ENC_PLAN): the running sums are made from the offsets as the caller left them, before the host has seen
+    // them -- arithmetic on their differences, nothing is addressed by them -- so that the totals arrive with the offsets in the one wait.
+    const bool dev_plan = e->enc.plan_choice == 2 || (e->enc.plan_choice == 0 && count >= ZK_ENC_PLAN_DEV_FRAMES);
+    ZkEncPlanSum *d_sums = nullptr, *totals = (ZkEncPlanSum *)(e->h_words + ZK_HW_ENC_PLAN);
+    if (dev_plan) {
+        if ((rc = zk_enc_reserve(e, e->enc.plan, ((size_t)count + 1) * sizeof(ZkEncPlanSum) + 64, &d_sums))) return rc;
+        zk_launch_enc_plan_scan(st, (const uint64_t *)d_off, count, zke_prefix_hist(prefix_len) != 0, d_sums);
+        ZK_HIP(hipMemcpyAsync(totals, d_sums + count, sizeof(ZkEncPlanSum), hipMemcpyDeviceToHost, st));
+    }
+    ZK_HIP(hipStreamSynchronize(st));
+    uint64_t max_frame = 0;
+    if ((rc = zk_enc_list_check(off, count, &max_frame))) return rc;
+    const uint64_t n = off[count] - off[0];
+    if (n && !d_src) return ZK_ERR_ARGUMENT;
+    zk_enc_args a{d_src ? (const uint8_t *)d_src + off[0] : nullptr, n, (uint32_t)(max_frame ? max_frame : 1), level, checksum, prefix_len ? d_prefix : nullptr, prefix_len,
+                  d_dst, dst_cap, d_c_sizes, d_d_sizes, cdict, off, count};
+    if (dev_plan) { a.d_list = (const uint64_t *)d_off; a.d_plan_sums = d_sums; a.plan_totals = totals; }
+    if ((rc = zk_encode_enqueue(e, a, st, nullptr))) return rc;
+    uint64_t total = 0;
+    if ((rc = zk_encode_finish(e, st, &total))) return rc;
     if (written_out) *written_out = total;
     return 0;
 }

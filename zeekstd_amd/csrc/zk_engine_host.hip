@@ -27,6 +27,7 @@
 #include "../../include/zeekstd_amd.h"
 #include "zk_engine.h"
 #include "zk_kernels.h"
+#include "zk_enc_plan.h"
 
 // ---------------------------------------------------------------------------------------------- worker threads
 namespace {
@@ -719,10 +720,10 @@ extern "C" int zk_decode_frames_prefix(zk_engine *e, const uint8_t *comp, uint64
 
 // ---------------------------------------------------------------------------------------------- encode
 int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_size, int level, int checksum, const void *d_prefix,
-                   uint64_t prefix_len, zk_host_sink sink, void *user, const zk_cdict *cdict)
+                   uint64_t prefix_len, zk_host_sink sink, void *user, const zk_cdict *cdict, const uint64_t *list, uint32_t list_count)
 {
-    if (!e || frame_size == 0 || frame_size > ZK_SEEKABLE_MAX_FRAME_SIZE || !sink || (n && !src)) return ZK_ERR_ARGUMENT;
-    const uint64_t nf64 = n == 0 ? 1 : (n + frame_size - 1) / frame_size;
+    if (!e || frame_size == 0 || frame_size > ZK_SEEKABLE_MAX_FRAME_SIZE || !sink || (n && !src) || (list && !list_count)) return ZK_ERR_ARGUMENT;
+    const uint64_t nf64 = list ? list_count : n == 0 ? 1 : (n + frame_size - 1) / frame_size;
     if (nf64 > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
     ZK_HIP(hipSetDevice(e->device));
     zk_hostpipe *hp = nullptr;
@@ -737,12 +738,26 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
     if (per * frame_size > (2048ull << 20)) per = (2048ull << 20) / frame_size;
     if (per < 1) per = 1;
     if (nf64 <= per + per / 4) per = nf64;                   // no short tail chunk
-    const size_t nchunks = (size_t)((nf64 + per - 1) / per);
+    // a frame list: groups of whole frames to the same targets by bytes; `per` becomes the most frames, max_in the most bytes of a chunk
+    std::vector<uint32_t> cuts;                              // first frame of chunk i, and the count behind the last
+    uint64_t list_max_in = 0;
+    if (list) {
+        per = 0;
+        for (uint32_t f0 = 0; f0 < list_count;) {
+            const uint32_t f1 = zke_list_chunk_end(list, list_count, f0, 256ull << 20, 128, 2048ull << 20);
+            cuts.push_back(f0);
+            if (f1 - f0 > per) per = f1 - f0;
+            if (list[f1] - list[f0] > list_max_in) list_max_in = list[f1] - list[f0];
+            f0 = f1;
+        }
+        cuts.push_back(list_count);
+    }
+    const size_t nchunks = list ? cuts.size() - 1 : (size_t)((nf64 + per - 1) / per);
     const bool src_pinned = n == 0 || zk_is_pinned(src);
     const bool small = nchunks == 1 && n <= (4u << 20);
     if (!small) { if ((rc = zk_hostpipe_rings(e, hp))) return rc; }                 // the compressed bytes travel back through the ring
-    const uint64_t max_in = per * frame_size < n ? per * frame_size : n;
-    const uint64_t max_bound = cdict ? zk_compress_bound_dict(max_in, frame_size) : zk_compress_bound(max_in, frame_size);
+    const uint64_t max_in = list ? list_max_in : per * frame_size < n ? per * frame_size : n;
+    const uint64_t max_bound = list ? zk_compress_bound_list(max_in, (uint32_t)per, cdict != nullptr) : cdict ? zk_compress_bound_dict(max_in, frame_size) : zk_compress_bound(max_in, frame_size);
     if (small) { if ((rc = zk_pin_reserve(e, hp->pin_small, hp->pin_small_cap, (size_t)max_in + (size_t)max_bound + 256))) return rc; }
     if ((rc = zk_pin_reserve(e, hp->pin_meta, hp->pin_meta_cap, (size_t)per * 8 * 2 + 64))) return rc;     // (c, d) sizes of two chunks
     ZkRegWindow wsrc;                                       // (after every allocation that can fail: its pool tasks point at this frame)
@@ -752,6 +767,7 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
     hsrc.mem = src;
 
     auto chunk_range = [&](size_t i, uint64_t &f0, uint64_t &nf, uint64_t &b0, uint64_t &bn) {
+        if (list) { f0 = cuts[i]; nf = cuts[i + 1] - f0; b0 = list[f0] - list[0]; bn = list[f0 + nf] - list[f0]; return; }
         f0 = (uint64_t)i * per; nf = nf64 - f0 < per ? nf64 - f0 : per;
         b0 = f0 * frame_size; bn = n - b0 < nf * frame_size ? n - b0 : nf * frame_size;
     };
@@ -768,7 +784,7 @@ int zk_host_encode(zk_engine *e, const uint8_t *src, uint64_t n, uint32_t frame_
         uint64_t f0, nf, b0, bn; chunk_range(i, f0, nf, b0, bn);
         zk_hostpipe::Slot &s = hp->es[i & 1];
         int r0;
-        zk_enc_args a{s.in.p, bn, frame_size, level, checksum, d_prefix, d_prefix ? prefix_len : 0, s.out.p, 0, nullptr, nullptr, cdict};
+        zk_enc_args a{s.in.p, bn, frame_size, level, checksum, d_prefix, d_prefix ? prefix_len : 0, s.out.p, 0, nullptr, nullptr, cdict, list ? list + f0 : nullptr, list ? (uint32_t)nf : 0u};
         a.dst_cap = zk_enc_bound(a);
         if ((r0 = zk_devbuf_reserve(e, s.out, (size_t)a.dst_cap + 64))) return r0;      // the chunk two back has been handed to the sink by now
         if ((r0 = zk_devbuf_reserve(e, s.meta, (size_t)nf * 8 + 64))) return r0;
@@ -887,6 +903,35 @@ extern "C" int zk_encode_frames_prefix(zk_engine *e, const uint8_t *src, uint64_
     if (s.overflow) return -(int)ZK_E_DST_TOO_SMALL;
     if (rc) return rc;
     if (n_frames_out) *n_frames_out = s.nf;
+    if (written_out) *written_out = s.pos;
+    return 0;
+}
+
+// frames of caller-given sizes through the same pipeline: chunks are groups of whole frames (zke_list_chunk_end)
+extern "C" int zk_encode_frame_list(zk_engine *e, const uint8_t *src, const uint64_t *off, uint32_t count, int level, int checksum,
+                                    const uint8_t *prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                                    uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint64_t *written_out)
+{
+    if (!e || (cdict && cdict->e != e) || (cdict && prefix && prefix_len)) return ZK_ERR_ARGUMENT;
+    if (count > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
+    if (count == 0) { if (written_out) *written_out = 0; return 0; }
+    if (!off || !dst) return ZK_ERR_ARGUMENT;
+    uint64_t max_frame = 0;
+    int rc;
+    if ((rc = zk_enc_list_check(off, count, &max_frame))) return rc;
+    const uint64_t n = off[count] - off[0];
+    if (n && !src) return ZK_ERR_ARGUMENT;
+    const void *d_prefix = nullptr;
+    uint64_t tail = 0;
+    if (cdict) { d_prefix = cdict->content_len ? cdict->d_content : nullptr; tail = cdict->content_len; }
+    else {
+        tail = prefix ? zke_ldm_usable(prefix_len) : 0;     // only the tail the matcher can reach is staged
+        if ((rc = zk_engine_stage_prefix(e, nullptr, tail ? prefix + (prefix_len - tail) : nullptr, tail, true, &d_prefix))) return rc;
+    }
+    ZkBufSink s{e, dst, dst_cap, 0, c_sizes, d_sizes, 0, false};
+    rc = zk_host_encode(e, src ? src + off[0] : nullptr, n, (uint32_t)(max_frame ? max_frame : 1), level, checksum, d_prefix, tail, zk_buf_sink, &s, cdict, off, count);
+    if (s.overflow) return -(int)ZK_E_DST_TOO_SMALL;
+    if (rc) return rc;
     if (written_out) *written_out = s.pos;
     return 0;
 }

@@ -118,7 +118,7 @@ class Engine:
 
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
-               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16}
+               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -268,6 +268,42 @@ class Engine:
         if rc != 0:
             self._raise(rc)
         return nfo.value, wr.value
+
+    def encode_frame_list(self, data, offsets, level=1, checksum=False, prefix=None, dictionary=None):
+        """zk_encode_frame_list: one zstd frame per entry of `offsets` (len(frames) + 1 non-decreasing prefix sums into data; the array the
+        decode calls take as d_off).  Returns (compressed payload bytes, [(c_size, d_size), ...]).  prefix / dictionary as encode_frames."""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        off = _u64(offsets)
+        count = max(len(off) - 1, 0)
+        if dictionary is not None and prefix:
+            raise ValueError("a prefix and a dictionary exclude each other at this level")
+        n = int(off[count] - off[0]) if count and off[count] >= off[0] else 0
+        cap = int(lib.zk_compress_bound_list(n, count, int(dictionary is not None)))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        cs = np.zeros(max(count, 1), np.uint32)
+        ds = np.zeros(max(count, 1), np.uint32)
+        wr = C.c_uint64()
+        pre = np.frombuffer(bytes(prefix), dtype=np.uint8) if prefix else None
+        rc = lib.zk_encode_frame_list(self._h, data.ctypes.data if data.size else None, off.ctypes.data, count, level, int(checksum),
+                                      pre.ctypes.data if pre is not None else None, pre.size if pre is not None else 0,
+                                      dictionary._h if dictionary is not None else None, out.ctypes.data, cap, cs.ctypes.data, ds.ctypes.data,
+                                      C.byref(wr))
+        if rc != 0:
+            self._raise(rc)
+        return out[:wr.value].tobytes(), list(zip(cs[:count].tolist(), ds[:count].tolist()))
+
+    def encode_frame_list_dev(self, d_src, d_off, count, level, checksum, d_dst, dst_cap, d_c_sizes=None, d_d_sizes=None, d_prefix=None,
+                              prefix_len=0, dictionary=None, stream=None):
+        """zk_encode_frame_list_dev: device tensors in and out, d_off = count + 1 uint64 prefix sums on the device.  Returns bytes written."""
+        wr = C.c_uint64()
+        rc = lib.zk_encode_frame_list_dev(self._h, self._ptr(d_src) if d_src is not None else None, self._ptr(d_off) if d_off is not None else None,
+                                          count, level, int(checksum), self._ptr(d_prefix) if d_prefix is not None else None, prefix_len,
+                                          dictionary._h if dictionary is not None else None, self._ptr(d_dst) if d_dst is not None else None, dst_cap,
+                                          self._ptr(d_c_sizes) if d_c_sizes is not None else None,
+                                          self._ptr(d_d_sizes) if d_d_sizes is not None else None, C.byref(wr), stream)
+        if rc != 0:
+            self._raise(rc)
+        return wr.value
 
     def xxh64_frames(self, data, off):
         data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
