@@ -115,9 +115,12 @@ enum {
     ZK_CHOICE_ENC_DICT_SLICE_KIB = 16, /* zk_encode_frames_dict*: KiB of [dictionary content | frame] records staged for the matcher at a time (1..2^22;
                                         * 0 = 2^20, 1 GiB).  A longer input is staged and matched slice after slice of whole frames over that buffer, never
                                         * less than one frame; the bytes produced do not depend on it */
-    ZK_CHOICE_ENC_PLAN = 17            /* zk_encode_frame_list_dev: where the frame / block / segment records are made: 0 = by the number of frames,
+    ZK_CHOICE_ENC_PLAN = 17,           /* zk_encode_frame_list_dev: where the frame / block / segment records are made: 0 = by the number of frames,
                                         * 1 = on the host (written and uploaded, 160 bytes per frame), 2 = on the device from the offsets.  The same
                                         * records, so the same bytes */
+    ZK_CHOICE_TRAIN_TRIAL_KIB = 18     /* zk_train_dictionary*: KiB of samples above which the candidates are tried, and the tables measured, on every j-th
+                                        * sample (1..2^22; 0 = 2^16, 64 MiB).  Unlike the keys above it is part of the function: it decides which samples
+                                        * the choice of k and the tables see.  The tests reach the rule with small inputs through it */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -308,6 +311,7 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *   zk_cdict_create / _free / _id, zk_encode_frames_dict[_dev],                     served    served    served     (the same; a zk_cdict is no decode state)
  *     zk_raw_encoder_set_dictionary, zk_encoder_set_dictionary
  *   zk_encode_frame_list[_dev]                                                      served    served    served     (the encoder's scratch, as the rows above)
+ *   zk_train_dictionary[_dev]                                                       served    served    served     (the encoder's scratch and its frame-list route)
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
  *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
@@ -434,6 +438,58 @@ int zk_encode_frame_list_dev(zk_engine *e, const void *d_src, const void *d_off,
 int zk_encode_frame_list(zk_engine *e, const uint8_t *src, const uint64_t *off, uint32_t count, int level, int checksum,
                          const uint8_t *prefix, uint64_t prefix_len, const zk_cdict *cdict,
                          uint8_t *dst, uint64_t dst_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint64_t *written);
+
+/* ---- A dictionary trained on the device from the caller's samples (what ZDICT_trainFromBuffer does on the host; the reference has no
+ * counterpart: it is handed contexts that already hold a dictionary).  off[count + 1]: the prefix sums of zk_encode_frame_list, sample i is
+ * samples[off[i], off[i + 1]); off[0] need not be 0, empty samples are allowed.  p == NULL: every default.
+ * The content is chosen as fastCover chooses it, without its per-segment duplicate map: every d-mer that lies inside one
+ * sample is hashed to f bits and counted; the samples' N bytes are cut into E = max(1, min(content_cap / k, N / (10 k))) epochs of N / E
+ * positions; epoch after epoch the segment of k bytes inside the epoch whose k - d + 1 d-mers have the largest sum of counts joins the content
+ * (the lowest position on ties; nothing when the sum is 0) and the counts of its d-mers are cleared; rounds over the epochs until no further
+ * segment fits or a round adds nothing.  The first segment taken lies last, nearest the data.  content_cap = min(cap - 512, 2^27 - 1): 512
+ * bytes of the capacity are kept for a formatted dictionary's header whatever is written, and the matcher reaches no further back.  When no
+ * segment is taken (fewer bytes than k in an epoch) the content is the last min(N, content_cap) bytes of the samples.
+ * k == 0: the candidates {64, 128, 256, 512} that are <= cap / 4 are each selected (a workgroup each), the samples are encoded against every
+ * candidate content with zk_encode_frame_list_dev's own route at `level` (the content as a raw-content dictionary), and the candidate with the
+ * smallest total is kept, the smaller k on a tie.  Samples of at most 64 MiB in all are all encoded; above that every j-th sample is (0, j,
+ * 2 j, ...), for the smallest j whose samples total at most 64 MiB (the first sample alone when no j does) -- these TRIAL SAMPLES are also what
+ * the tables are measured on and what the report's two compressed totals count.  The content is always selected from all samples.
+ * The result is a pure function of the arguments (integer atomics and sums only); both entry points give identical bytes.
+ * What is written (RFC 8878 section 5): magic, Dictionary_ID, Huffman tree description, FSE descriptions of offsets, match lengths and literal
+ * lengths, the repeat offsets 1 / 4 / 8, the content (moved up to the header: the header takes less than its 512 bytes).  The tables are the
+ * statistics of the engine's own matcher: the encode stages up to and including the match stage run once more over the samples with the
+ * chosen content as the prefix, and every literal byte and every sequence's three codes are counted (zk_k_train_stats).  The matcher emits a
+ * repeat code only after a sequence of the same block, so the dictionary's repeat offsets never enter: they are 1 / 4 / 8.  Every literal value
+ * and every code (LL 0..35, ML 0..52, OF 0..30) gets a count of at least 1, so that zk_encode_frames_dict*'s rules always allow the Treeless
+ * first block and Repeat_Mode; Huffman code lengths are at most 11 and their 255 weights are written FSE-compressed; the FSE tables are
+ * normalised at accuracy logs 9 / 9 / 8 (LL / ML / OF).  dict_id == 0: 32768 + XXH64(content) mod (2^31 - 65536), inside libzstd's private range.
+ * The result is a dictionary zk_dict_create accepts and libzstd loads.  flags: ZK_TRAIN_RAW_CONTENT writes the content alone, a raw-content
+ * dictionary (ID 0): exactly the formatted result's content.
+ * ZK_ERR_ARGUMENT, and nothing written, for: count == 0; cap < 1024; NULL dict_out / written / off; d other than 0 / 6 / 8; f other than 0 or
+ * 10 ... 24; k other than 0 or 16 ... 4096, or k > cap / 4; an unknown flag; a decreasing list; 2^32 or more sample bytes; fewer than
+ * 8 samples of at least d bytes; a sample above ZK_SEEKABLE_MAX_FRAME_SIZE.  count > ZK_SEEKABLE_MAX_FRAMES: ZK_ERR_FRAME_INDEX_TOO_LARGE, decided
+ * before the list is read.
+ * report (optional): the segment length kept, the segments taken, the content's and the header's bytes (0 for raw content), and the samples'
+ * bytes: as given (all of them) / the trial samples encoded at `level` against the result's CONTENT as a raw-content dictionary / the trial
+ * samples encoded without a dictionary.
+ * The device entry point synchronises its stream; dict_out, written and report are host memory in both. */
+#define ZK_TRAIN_RAW_CONTENT 1u
+typedef struct zk_train_params {
+    uint32_t k;        /* segment length, 16 ... 4096; 0 = try the built-in set {64, 128, 256, 512} (those <= cap / 4) and keep the best */
+    uint32_t d;        /* d-mer length, 6 or 8; 0 = 8 */
+    uint32_t f;        /* log2 of the frequency table, 10 ... 24; 0 = 20 */
+    int level;         /* encoder level the statistics, the choice between candidates and the report are taken at; 0 = 1 */
+    uint32_t dict_id;  /* 0 = derived from the content's XXH64 into [32768, 2^31 - 32768) */
+    uint32_t flags;    /* ZK_TRAIN_RAW_CONTENT: write the content alone (a raw-content dictionary) */
+} zk_train_params;
+typedef struct zk_train_report {
+    uint32_t k_chosen, segments, content_bytes, header_bytes;
+    uint64_t sample_bytes, compressed_with, compressed_without;
+} zk_train_report;
+int zk_train_dictionary_dev(zk_engine *e, const void *d_samples, const void *d_off, uint32_t count, const zk_train_params *p,
+                            uint8_t *dict_out, size_t cap, size_t *written, zk_train_report *report, void *stream);
+int zk_train_dictionary(zk_engine *e, const uint8_t *samples, const uint64_t *off, uint32_t count, const zk_train_params *p,
+                        uint8_t *dict_out, size_t cap, size_t *written, zk_train_report *report);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside

@@ -28,6 +28,20 @@ if "torch" not in sys.modules and not os.environ.get("ZEEKSTD_AMD_NO_TORCH"):
 lib = C.CDLL(LIB_PATH)
 
 _P = C.c_void_p
+
+
+class TrainParams(C.Structure):
+    """zk_train_params"""
+    _fields_ = [("k", C.c_uint32), ("d", C.c_uint32), ("f", C.c_uint32), ("level", C.c_int), ("dict_id", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class TrainReport(C.Structure):
+    """zk_train_report"""
+    _fields_ = [("k_chosen", C.c_uint32), ("segments", C.c_uint32), ("content_bytes", C.c_uint32), ("header_bytes", C.c_uint32),
+                ("sample_bytes", C.c_uint64), ("compressed_with", C.c_uint64), ("compressed_without", C.c_uint64)]
+
+
+TRAIN_RAW_CONTENT = 1
 _sig = {
     "zk_abi_version": (C.c_int, []),
     "zk_error_name": (C.c_char_p, [C.c_int]),
@@ -87,6 +101,10 @@ _sig = {
                                            C.POINTER(C.c_uint64), _P]),
     "zk_encode_frame_list": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P,
                                        C.POINTER(C.c_uint64)]),
+    "zk_train_dictionary_dev": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(TrainParams), _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                          C.POINTER(TrainReport), _P]),
+    "zk_train_dictionary": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(TrainParams), _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.POINTER(TrainReport)]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

@@ -9,7 +9,8 @@
 
 enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_EXEC, ZK_K_XXH64, ZK_K_STATUS,
        ZK_K_ENC_MATCH, ZK_K_ENC_ENTROPY, ZK_K_ENC_COMPACT, ZK_K_ENC_XXH64, ZK_K_ENC_FSE_BUILD, ZK_K_ENC_DENSE,
-       ZK_K_RANGE_PLAN, ZK_K_RANGE_PIECES, ZK_K_RANGE_GATHER, ZK_K_RANGE_STATUS, ZK_NKERNELS };
+       ZK_K_RANGE_PLAN, ZK_K_RANGE_PIECES, ZK_K_RANGE_GATHER, ZK_K_RANGE_STATUS,
+       ZK_K_TRAIN_COUNT, ZK_K_TRAIN_SELECT, ZK_K_TRAIN_STATS, ZK_NKERNELS };
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };
@@ -84,7 +85,9 @@ struct zk_engine {
         zk_devbuf dense;                    // dense far history (level 0 / >= 3, frames beyond the ring's reach): a candidate per input byte (ZkEncLdm::dense)
         zk_devbuf ldm;                      // prefix beyond the matcher's ring: the long-distance table (ZkEncLdm)
         zk_devbuf plan;                     // a frame list planned on the device: the frames' running sums (ZkEncPlanSum, zk_enc_plan_dev.h)
+        zk_devbuf train, train_src;         // zk_train_dictionary*: its scratch (zk_train.hip); the host entry point's upload of the samples and their offsets
         int plan_choice = 0;                // ZK_CHOICE_ENC_PLAN
+        uint64_t train_trial_bytes = 0;     // zk_train_dictionary*: sample bytes the candidates are tried on (0 = 64 MiB), ZK_CHOICE_TRAIN_TRIAL_KIB
         uint64_t dense_slice_bytes = 0;     // input bytes the dense scratch is reserved for (0 = 4 GiB), ZK_CHOICE_ENC_DENSE_SLICE_KIB
         uint64_t dict_slice_bytes = 0;      // dictionary route: bytes of [content tail | frame] records staged at a time (0 = 1 GiB), ZK_CHOICE_ENC_DICT_SLICE_KIB
         ZkEncTables tables;
@@ -169,6 +172,8 @@ struct zk_cdict {
     uint64_t content_len = 0;
     ZkEncDictDev *d_tab = nullptr;          // formatted dictionaries: the compression side of the four tables
 };
+// where the matcher left its output: what an encode that stops behind zk_enc_match hands back (zk_enc_args::matched)
+struct ZkEncMatched { const ZkEncBlock *blocks; uint32_t nb; const uint64_t *seqs; const uint8_t *lits; };
 struct zk_enc_args {
     const void *d_src; uint64_t n; uint32_t frame_size; int level, checksum;
     const void *d_prefix; uint64_t prefix_len; void *d_dst; uint64_t dst_cap; void *d_c_sizes, *d_d_sizes;
@@ -182,6 +187,9 @@ struct zk_enc_args {
     // ... planned on the device (zk_enc_plan_dev.h): the caller's offsets there, the frames' running sums (zk_k_enc_plan_scan has run) and, on the
     // host, the totals behind them; all null: the host plans
     const uint64_t *d_list = nullptr; const struct ZkEncPlanSum *d_plan_sums = nullptr, *plan_totals = nullptr;
+    // run the stages up to and including zk_enc_match only, and say here where the blocks, sequences and literals lie (device memory of the
+    // engine, valid until its next encode); nothing is written to d_dst.  nullptr: the whole encode
+    ZkEncMatched *matched = nullptr;
 };
 // the entry points' check of a frame list (ZK_ERR_ARGUMENT / ZK_ERR_FRAME_INDEX_TOO_LARGE); *max_frame: the largest frame
 int zk_enc_list_check(const uint64_t *off, uint32_t count, uint64_t *max_frame);
@@ -189,6 +197,9 @@ int zk_enc_list_check(const uint64_t *off, uint32_t count, uint64_t *max_frame);
 uint64_t zk_enc_bound(const zk_enc_args &a);
 int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32_t *nf_out);
 int zk_encode_finish(zk_engine *e, hipStream_t st, uint64_t *written_out);
+// zk_encode_frame_list_dev on the prefix route up to and including the match stage (zk_enc_args::matched); the stream is left running
+int zk_encode_frame_list_matched(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, const void *d_prefix, uint64_t prefix_len,
+                                 void *d_dst, uint64_t dst_cap, ZkEncMatched *matched, hipStream_t st);
 
 // ---- host pipeline, C++ face (the C ABI's host-pointer functions and the zeekstd:: host classes sit on these)
 // Where the compressed bytes of a host decode come from: contiguous memory, or a pull callback that delivers the n bytes

@@ -411,10 +411,13 @@ int zk_encode_enqueue(zk_engine *e, const zk_enc_args &a, hipStream_t st, uint32
         zk_enc_entropy, zk_enc_sizes_total, zk_enc_fit_check, zk_enc_assemble};
     ZkEncLayout L;
     L.cks_beside = false;
-    for (auto stage : stages) if (const int rc = stage(e, a, L, st)) {
-        // the checksum kernel on the second queue reads the caller's source: nothing of this call runs on once it has returned
-        if (L.cks_beside) (void)hipStreamSynchronize(e->enc.aux);
-        return rc;
+    for (auto stage : stages) {
+        if (const int rc = stage(e, a, L, st)) {
+            // the checksum kernel on the second queue reads the caller's source: nothing of this call runs on once it has returned
+            if (L.cks_beside) (void)hipStreamSynchronize(e->enc.aux);
+            return rc;
+        }
+        if (a.matched && stage == zk_enc_match) { *a.matched = ZkEncMatched{L.d_blocks, L.pl.nb, L.seqs, L.lits}; break; }
     }
     if (nf_out) *nf_out = L.pl.nf;
     return 0;
@@ -508,9 +511,9 @@ extern "C" int zk_encode_frames_dict_dev(zk_engine *e, const void *d_src, uint64
 // The offsets come to the host first (8 bytes per frame, one wait for `st`): the list is checked there, and the slices, the far-history tables
 // and -- unless the device makes it -- the plan are host arithmetic on it.  From there on it is the one pipeline above -- zk_enc_args::list --
 // on the plain, the prefix or the dictionary route.
-extern "C" int zk_encode_frame_list_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, int checksum,
-                                        const void *d_prefix, uint64_t prefix_len, const zk_cdict *cdict,
-                                        void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint64_t *written_out, void *stream)
+static int zk_enc_frame_list_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, int checksum,
+                                 const void *d_prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                                 void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint64_t *written_out, void *stream, ZkEncMatched *matched)
 {
     if (!e || (cdict && cdict->e != e) || (cdict && d_prefix && prefix_len)) return ZK_ERR_ARGUMENT;
     if (count > ZK_SEEKABLE_MAX_FRAMES) return ZK_ERR_FRAME_INDEX_TOO_LARGE;
@@ -541,9 +544,22 @@ extern "C" int zk_encode_frame_list_dev(zk_engine *e, const void *d_src, const v
     zk_enc_args a{d_src ? (const uint8_t *)d_src + off[0] : nullptr, n, (uint32_t)(max_frame ? max_frame : 1), level, checksum, prefix_len ? d_prefix : nullptr, prefix_len,
                   d_dst, dst_cap, d_c_sizes, d_d_sizes, cdict, off, count};
     if (dev_plan) { a.d_list = (const uint64_t *)d_off; a.d_plan_sums = d_sums; a.plan_totals = totals; }
+    a.matched = matched;
     if ((rc = zk_encode_enqueue(e, a, st, nullptr))) return rc;
+    if (matched) return 0;
     uint64_t total = 0;
     if ((rc = zk_encode_finish(e, st, &total))) return rc;
     if (written_out) *written_out = total;
     return 0;
+}
+extern "C" int zk_encode_frame_list_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, int checksum,
+                                        const void *d_prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                                        void *d_dst, uint64_t dst_cap, void *d_c_sizes, void *d_d_sizes, uint64_t *written_out, void *stream)
+{
+    return zk_enc_frame_list_dev(e, d_src, d_off, count, level, checksum, d_prefix, prefix_len, cdict, d_dst, dst_cap, d_c_sizes, d_d_sizes, written_out, stream, nullptr);
+}
+int zk_encode_frame_list_matched(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, const void *d_prefix, uint64_t prefix_len,
+                                 void *d_dst, uint64_t dst_cap, ZkEncMatched *matched, hipStream_t st)
+{
+    return zk_enc_frame_list_dev(e, d_src, d_off, count, level, 0, d_prefix, prefix_len, nullptr, d_dst, dst_cap, nullptr, nullptr, nullptr, st, matched);
 }

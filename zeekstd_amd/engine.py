@@ -43,6 +43,11 @@ class Dictionary:
             lib.zk_dict_free(self._h)
             self._h = None
 
+    @classmethod
+    def train(cls, engine, samples, offsets=None, size=112640, **params):
+        """A Dictionary of the bytes Engine.train_dictionary makes of the samples (same arguments)."""
+        return cls(engine.train_dictionary(samples, offsets, size, **params))
+
 
 class EncodeDictionary:
     """A dictionary compiled for encoding on one engine (zk_cdict_create; the counterpart of ZSTD_CDict): its content and, for a formatted
@@ -118,7 +123,7 @@ class Engine:
 
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
-               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17}
+               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17, "train_trial_kib": 18}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -304,6 +309,48 @@ class Engine:
         if rc != 0:
             self._raise(rc)
         return wr.value
+
+    @staticmethod
+    def _train_params(k, d, f, level, dict_id, raw_content):
+        return _lib.TrainParams(k, d, f, level, dict_id, _lib.TRAIN_RAW_CONTENT if raw_content else 0)
+
+    def train_dictionary(self, samples, offsets=None, size=112640, k=0, d=0, f=0, level=0, dict_id=0, raw_content=False, report=False):
+        """zk_train_dictionary: a zstd dictionary of at most `size` bytes trained on the device.  samples: a list of bytes objects, or one
+        buffer with `offsets` (len(samples) + 1 non-decreasing prefix sums into it).  k / d / f / level / dict_id: zk_train_params, 0 = the
+        default; raw_content: the content alone (ZK_TRAIN_RAW_CONTENT).  Returns the dictionary's bytes; report=True: (bytes, dict of the
+        zk_train_report fields)."""
+        if offsets is None:
+            sizes = [len(x) for x in samples]
+            data = np.frombuffer(b"".join(bytes(x) for x in samples), dtype=np.uint8)
+            off = np.zeros(len(sizes) + 1, np.uint64)
+            off[1:] = np.cumsum(sizes, dtype=np.uint64)
+        else:
+            data = np.frombuffer(samples, dtype=np.uint8) if not isinstance(samples, np.ndarray) else samples
+            off = _u64(offsets)
+        out = np.empty(max(int(size), 1), np.uint8)
+        wr = C.c_size_t()
+        rep = _lib.TrainReport()
+        par = self._train_params(k, d, f, level, dict_id, raw_content)
+        rc = lib.zk_train_dictionary(self._h, data.ctypes.data if data.size else None, off.ctypes.data, max(len(off) - 1, 0), C.byref(par),
+                                     out.ctypes.data, int(size), C.byref(wr), C.byref(rep))
+        if rc != 0:
+            self._raise(rc)
+        got = out[:wr.value].tobytes()
+        return (got, {n: int(getattr(rep, n)) for n, _ in rep._fields_}) if report else got
+
+    def train_dictionary_dev(self, d_samples, d_off, count, size=112640, k=0, d=0, f=0, level=0, dict_id=0, raw_content=False, report=False, stream=None):
+        """zk_train_dictionary_dev: the samples and their count + 1 uint64 offsets are device tensors (or raw pointers); the dictionary's
+        bytes come back on the host as from train_dictionary."""
+        out = np.empty(max(int(size), 1), np.uint8)
+        wr = C.c_size_t()
+        rep = _lib.TrainReport()
+        par = self._train_params(k, d, f, level, dict_id, raw_content)
+        rc = lib.zk_train_dictionary_dev(self._h, self._ptr(d_samples) if d_samples is not None else None, self._ptr(d_off) if d_off is not None else None,
+                                         count, C.byref(par), out.ctypes.data, int(size), C.byref(wr), C.byref(rep), stream)
+        if rc != 0:
+            self._raise(rc)
+        got = out[:wr.value].tobytes()
+        return (got, {n: int(getattr(rep, n)) for n, _ in rep._fields_}) if report else got
 
     def xxh64_frames(self, data, off):
         data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
