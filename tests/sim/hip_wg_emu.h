@@ -5,7 +5,9 @@
 //   wave collectives (__ballot, readlane, ds_bpermute, update_dpp row_shr:1, wave_barrier) -> the 64 lanes of a wave
 //                             deposit their value and park until the wave is complete; they must be called by all 64
 //                             lanes (wave-uniform control flow), as the kernels under test do
-//   atomicCAS / atomicMin / atomicMax / atomicAdd -> plain (fibers are cooperative)
+//   __shfl / __shfl_xor (32- and 64-bit), __any -> collectives like __ballot; __builtin_amdgcn_alignbit, uint4 / make_uint4
+//   atomicCAS / atomicMin / atomicMax / atomicAdd / atomicOr -> plain (fibers are cooperative)
+//   zk_xxh64.h's hooks (ZKX_XCC_ID, ZKX_CLOCK, ZKX_SLEEP, ZKX_ACQUIRE, ZKX_PROG_LOAD) -> a scripted neighbour: see POLLING below
 //   gridDim, blockIdx.x / .y -> what emu_run_workgroup was told (defaults: a grid of one workgroup)
 // The scheduler visits the lanes in ascending order, or -- emu_set_lane_order(true) -- in descending order: a kernel whose result does
 // not depend on which lane reaches an atomic first gives the same output under both.
@@ -94,6 +96,48 @@ static inline uint32_t emu_atomic_cas(uint32_t *p, uint32_t cmp, uint32_t val) {
 static inline uint32_t emu_atomic_min(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v < old) *p = v; return old; }
 static inline uint32_t emu_atomic_max(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v > old) *p = v; return old; }
 static inline uint32_t emu_atomic_add(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old + v; return old; }
+template <typename T> static inline T emu_atomic_or(T *p, T v) { const T old = *p; *p = old | v; return old; }
+// __shfl / __shfl_xor (width 64) for 32- and 64-bit values, __any: collectives like __ballot
+static inline uint32_t emu_shfl32(uint32_t v, uint32_t src) { return emu_collect(v)[src & 63]; }            // (src is read before the lane parks)
+static inline uint32_t emu_shfl(uint32_t v, int src, int) { return emu_shfl32(v, (uint32_t)src); }
+static inline int emu_shfl(int v, int src, int) { return (int)emu_shfl32((uint32_t)v, (uint32_t)src); }
+static inline uint64_t emu_shfl(uint64_t v, int src, int)
+{
+    const uint32_t lo = emu_shfl32((uint32_t)v, (uint32_t)src), hi = emu_shfl32((uint32_t)(v >> 32), (uint32_t)src);
+    return ((uint64_t)hi << 32) | lo;
+}
+template <typename T> static inline T emu_shfl_xor(T v, int mask, int w) { return emu_shfl(v, (int)((g_emu.lanes[g_emu.cur].tid & 63) ^ (uint32_t)mask), w); }
+static inline bool emu_any(bool p) { return emu_ballot(p) != 0; }
+static inline uint32_t emu_alignbit(uint32_t hi, uint32_t lo, uint32_t s) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (s & 31)); }
+struct uint4 { uint32_t x, y, z, w; };
+static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
+
+// POLLING (zk_xxh64.h's hooks: a kernel that follows words another kernel writes).  Nothing else runs while a workgroup is emulated, so
+// the other kernel is a script: `on_poll` is called ONCE per poll of a wave, at the kernel's sleep, when all 64 lanes have arrived and
+// none is between the load of a word and the verdict on it -- there, and nowhere else, progress words, the bytes they announce and the
+// clock change.  A verdict that is wave-uniform on the device (readfirstlane, zk_uni: identities here) is then uniform here too, whatever
+// the lane order.  `max_polls` bounds a run: a kernel that polls more often than its patience allows is cancelled -- the lanes are
+// abandoned where they are, emu_run_workgroup returns and emu_cancelled() says so -- instead of spinning for ever.  (Abandoned: the lane
+// that trips the bound yields for ever and no fiber's stack is unwound, so nothing a kernel holds may need a destructor -- true of the
+// kernels here, which hold plain values.)  emu_poll counts arrivals in the wave's `count` / `gen`, the words emu_collect uses: like
+// every collective it must be reached by all 64 lanes, with no lane parked in another collective meanwhile -- wave-uniform control flow
+// between a collective and a sleep, which is what the device asks of these loops too.
+struct EmuPoll { std::function<void()> on_poll; uint64_t clock = 0, tick = 1, polls = 0, max_polls = ~0ull; uint32_t xcc = 0; };
+static EmuPoll g_emu_poll;
+static bool g_emu_cancel = false;
+static inline bool emu_cancelled() { return g_emu_cancel; }
+static inline void emu_poll()
+{
+    EmuWG &g = g_emu;
+    EmuWave &w = g.waves[g.lanes[g.cur].tid >> 6];
+    const uint64_t gen = w.gen;
+    if (++w.count < 64) { while (w.gen == gen) emu_yield(); return; }
+    w.count = 0;
+    g_emu_poll.clock += g_emu_poll.tick;
+    if (++g_emu_poll.polls > g_emu_poll.max_polls) { g_emu_cancel = true; for (;;) emu_yield(); }
+    if (g_emu_poll.on_poll) g_emu_poll.on_poll();
+    w.gen++;
+}
 
 static void emu_entry()
 {
@@ -124,8 +168,9 @@ static void emu_run_workgroup(uint32_t nthreads, uint32_t block, std::function<v
         l.ctx.uc_link = &g.sched;
         makecontext(&l.ctx, emu_entry, 0);
     }
-    while (g.live) {
-        for (uint32_t i = 0; i < nthreads; i++) {
+    g_emu_cancel = false;
+    while (g.live && !g_emu_cancel) {
+        for (uint32_t i = 0; i < nthreads && !g_emu_cancel; i++) {
             const uint32_t t = g.descending ? nthreads - 1 - i : i;
             if (g.lanes[t].done) continue;
             g.cur = t;
@@ -156,6 +201,17 @@ static void emu_run_workgroup(uint32_t nthreads, uint32_t block, std::function<v
 #define atomicMin(p, v) emu_atomic_min((p), (v))
 #define atomicMax(p, v) emu_atomic_max((p), (v))
 #define atomicAdd(p, v) emu_atomic_add((p), (v))
+#define atomicOr(p, v) emu_atomic_or((p), (__typeof__(*(p)))(v))
+#define __shfl(v, l, w) emu_shfl((v), (int)(l), (w))
+#define __shfl_xor(v, m, w) emu_shfl_xor((v), (m), (w))
+#define __any(p) emu_any(p)
+#define __popcll(x) __builtin_popcountll(x)
+#define __builtin_amdgcn_alignbit(hi, lo, s) emu_alignbit((hi), (lo), (s))
+#define ZKX_XCC_ID() (g_emu_poll.xcc)
+#define ZKX_CLOCK() (g_emu_poll.clock)
+#define ZKX_SLEEP(n) emu_poll()
+#define ZKX_ACQUIRE() ((void)0)
+#define ZKX_PROG_LOAD(p) (*(const volatile uint64_t *)(p))
 #define __ffs(x) __builtin_ffs(x)
 #define ZKE_FFBL(x) ((x) ? (uint32_t)__builtin_ctz(x) : 0xFFFFFFFFu)          /* v_ffbl_b32 */
 #define ZKE_FFBH(x) ((x) ? (uint32_t)__builtin_clz(x) : 0xFFFFFFFFu)          /* v_ffbh_u32 */
