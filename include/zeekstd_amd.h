@@ -118,9 +118,12 @@ enum {
     ZK_CHOICE_ENC_PLAN = 17,           /* zk_encode_frame_list_dev: where the frame / block / segment records are made: 0 = by the number of frames,
                                         * 1 = on the host (written and uploaded, 160 bytes per frame), 2 = on the device from the offsets.  The same
                                         * records, so the same bytes */
-    ZK_CHOICE_TRAIN_TRIAL_KIB = 18     /* zk_train_dictionary*: KiB of samples above which the candidates are tried, and the tables measured, on every j-th
+    ZK_CHOICE_TRAIN_TRIAL_KIB = 18,    /* zk_train_dictionary*: KiB of samples above which the candidates are tried, and the tables measured, on every j-th
                                         * sample (1..2^22; 0 = 2^16, 64 MiB).  Unlike the keys above it is part of the function: it decides which samples
                                         * the choice of k and the tables see.  The tests reach the rule with small inputs through it */
+    ZK_CHOICE_CDC_SLICE_KIB = 19       /* zk_chunk_boundaries*: input KiB whose candidates the engine holds at a time (1..2^22; 0 = 2^16, 64 MiB).  A longer
+                                        * input is marked and selected slice after slice, the chain's cut carried across.  The offsets do not depend on it;
+                                        * the scratch (up to 4 1/4 bytes per byte of a slice) does */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -312,6 +315,7 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *     zk_raw_encoder_set_dictionary, zk_encoder_set_dictionary
  *   zk_encode_frame_list[_dev]                                                      served    served    served     (the encoder's scratch, as the rows above)
  *   zk_train_dictionary[_dev]                                                       served    served    served     (the encoder's scratch and its frame-list route)
+ *   zk_chunk_boundaries[_dev], zk_encode_chunked[_dev]                              served    served    served     (the encoder's scratch and its frame-list route)
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
  *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
@@ -320,7 +324,8 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *   zk_engine_destroy                                                               served    served    served     (completes the batches first; their buffers hold the
  *                                                                                                                   results, their return codes are lost)
  * Functions that take no engine and no handle opened on one (zk_dict_*, zk_seek_table_*, zk_serializer_*, zk_host_alloc / _free,
- * zk_compress_bound, zk_compress_bound_dict, zk_shard_range, zk_set_collective_library) do not depend on any of this. */
+ * zk_compress_bound, zk_compress_bound_dict, zk_compress_bound_list, zk_compress_bound_chunked, zk_shard_range, zk_set_collective_library) do not
+ * depend on any of this. */
 int zk_decode_submit_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off,
                          const void *d_d_off, uint32_t first, uint32_t count, void *d_dst, uint64_t dst_cap,
                          int verify, void *d_frame_status, int *slot_out);
@@ -490,6 +495,55 @@ int zk_train_dictionary_dev(zk_engine *e, const void *d_samples, const void *d_o
                             uint8_t *dict_out, size_t cap, size_t *written, zk_train_report *report, void *stream);
 int zk_train_dictionary(zk_engine *e, const uint8_t *samples, const uint64_t *off, uint32_t count, const zk_train_params *p,
                         uint8_t *dict_out, size_t cap, size_t *written, zk_train_report *report);
+
+/* ---- Content-defined frame boundaries: where the frames end when the caller has no records to point at and a fixed grid will not do (one
+ * inserted byte shifts every later frame of a grid; cuts that follow the content fall back onto the old ones within a frame or two, and every
+ * untouched frame compresses to the same bytes as before -- what zchunk, casync and `zstd --rsyncable` cut by content for).  The reference has
+ * no counterpart.  off[count + 1] is the array zk_encode_frame_list[_dev] and later the decode calls take.
+ * THE RULE, a pure function of (src[0, n), min_size, avg_size, max_size):
+ *   - gear table G[b], b = 0..255, in 32-bit wrap-around arithmetic: x = (b + 1) * 0x9E3779B1; x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13;
+ *     x *= 0xC2B2AE35; x ^= x >> 16; G[b] = x
+ *   - hash of position p: h(p) = sum over j = 0..31 of G[src[p - j]] << j (mod 2^32), terms with p - j < 0 absent.  It is the gear recurrence
+ *     h = (h << 1) + G[byte], which forgets a byte after 32 steps: h(p) depends on src[p - 31 .. p] only
+ *   - candidate: with bits = log2(avg_size), p is a candidate iff h(p) >> (32 - bits) == 0 (the top bits: the low bits of a gear hash see only the
+ *     last few bytes).  A candidate at p offers the cut offset q = p + 1
+ *   - selection: off[0] = 0.  From a cut c < n, with lo = c + min_size and hi = min(c + max_size, n), the next cut is the smallest candidate offset
+ *     q with lo <= q <= hi, or hi if there is none.  Selection ends with the cut at n.  The last frame may be shorter than min_size, no other is;
+ *     no frame is longer than max_size.  n == 0: count = 1 and off = {0, 0}, the empty frame the other routes make.
+ * zk_chunk_params (p == NULL: every default): avg_size a power of two in [2^8, 2^24], 0 = 2^21 (zeekstd's default frame size); min_size in
+ * [64, avg_size], 0 = avg_size / 4; max_size in [min_size, ZK_SEEKABLE_MAX_FRAME_SIZE], 0 = min(4 * avg_size, 2^30); flags must be 0.  Anything
+ * else is ZK_ERR_ARGUMENT, decided before any work.
+ * What follows from the rule:
+ *   - a frame's end depends on its own bytes: min_size >= 64, so a candidate's 32-byte window lies inside the current frame, past its 32nd byte.
+ *     Where a frame ends depends only on where it starts and on its own bytes: two chains of cuts that share one cut share all later ones
+ *   - on incompressible data the mean frame is about min_size + avg_size when max_size is far away (316, 1306 and 5243 bytes measured on random
+ *     bytes for min / avg = 64 / 256, 256 / 1024 and 1024 / 4096)
+ *   - min_size == max_size == S gives exactly the cuts of frame_size = S, and therefore the bytes of zk_encode_frames*
+ * zk_chunk_boundaries_dev: d_src (any alignment) and d_off_out (uint64, off_cap + 1 entries) are device memory.  *count is always set; if count >
+ * off_cap nothing else is written and -70 comes back, so off_cap = 0 with a NULL array asks for the size.  (With off_cap >= n / min_size + 1,
+ * which no chain exceeds, the array is written in the one pass that finds the cuts; with less room the engine counts first and runs once more
+ * when the count fits.)  count > ZK_SEEKABLE_MAX_FRAMES is ZK_ERR_FRAME_INDEX_TOO_LARGE.  The call synchronises its stream.
+ * zk_chunk_boundaries (host pointers) uploads the source slice by slice; only the offsets come back.
+ * zk_encode_chunked[_dev] is zk_chunk_boundaries[_dev] followed by zk_encode_frame_list[_dev] on the plain, prefix or dictionary route: the frames
+ * are byte for byte what that call makes of the offsets.  The offsets array holds off_cap + 1 entries, c_sizes / d_sizes (may be NULL) off_cap
+ * each; *n_frames = count.  An off_cap that is too small is -70 before anything is encoded, with the destination untouched.
+ * dst_cap >= zk_compress_bound_chunked(n, p, with_dictionary) = zk_compress_bound_list(n, n / min_size + 1, with_dictionary) always suffices (0
+ * for parameters that would be refused); below it, -70 and "destination untouched" are as for zk_encode_frame_list_dev.
+ * The input is marked and selected in slices (ZK_CHOICE_CDC_SLICE_KIB), the chain's current cut carried from slice to slice and the 31-byte
+ * window read across the seam: the offsets do not depend on the slice, and the scratch is bounded by it, not by n. */
+typedef struct zk_chunk_params { uint32_t min_size, avg_size, max_size, flags; } zk_chunk_params;
+int zk_chunk_boundaries_dev(zk_engine *e, const void *d_src, uint64_t n, const zk_chunk_params *p, void *d_off_out, uint32_t off_cap,
+                            uint32_t *count, void *stream);
+int zk_chunk_boundaries(zk_engine *e, const uint8_t *src, uint64_t n, const zk_chunk_params *p, uint64_t *off_out, uint32_t off_cap,
+                        uint32_t *count);
+uint64_t zk_compress_bound_chunked(uint64_t n, const zk_chunk_params *p, int with_dictionary);
+int zk_encode_chunked_dev(zk_engine *e, const void *d_src, uint64_t n, const zk_chunk_params *p, int level, int checksum,
+                          const void *d_prefix, uint64_t prefix_len, const zk_cdict *cdict, void *d_dst, uint64_t dst_cap,
+                          void *d_off_out, uint32_t off_cap, void *d_c_sizes, void *d_d_sizes, uint32_t *n_frames,
+                          uint64_t *written, void *stream);
+int zk_encode_chunked(zk_engine *e, const uint8_t *src, uint64_t n, const zk_chunk_params *p, int level, int checksum,
+                      const uint8_t *prefix, uint64_t prefix_len, const zk_cdict *cdict, uint8_t *dst, uint64_t dst_cap,
+                      uint64_t *off_out, uint32_t off_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint32_t *n_frames, uint64_t *written);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside

@@ -41,6 +41,11 @@ class TrainReport(C.Structure):
                 ("sample_bytes", C.c_uint64), ("compressed_with", C.c_uint64), ("compressed_without", C.c_uint64)]
 
 
+class ChunkParams(C.Structure):
+    """zk_chunk_params"""
+    _fields_ = [("min_size", C.c_uint32), ("avg_size", C.c_uint32), ("max_size", C.c_uint32), ("flags", C.c_uint32)]
+
+
 TRAIN_RAW_CONTENT = 1
 _sig = {
     "zk_abi_version": (C.c_int, []),
@@ -105,6 +110,13 @@ _sig = {
                                           C.POINTER(TrainReport), _P]),
     "zk_train_dictionary": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(TrainParams), _P, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.POINTER(TrainReport)]),
+    "zk_chunk_boundaries_dev": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(ChunkParams), _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
+    "zk_chunk_boundaries": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(ChunkParams), _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "zk_compress_bound_chunked": (C.c_uint64, [C.c_uint64, C.POINTER(ChunkParams), C.c_int]),
+    "zk_encode_chunked_dev": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(ChunkParams), C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64,
+                                        _P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
+    "zk_encode_chunked": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(ChunkParams), C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64,
+                                    _P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

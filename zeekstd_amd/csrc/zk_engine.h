@@ -10,7 +10,7 @@
 enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_EXEC, ZK_K_XXH64, ZK_K_STATUS,
        ZK_K_ENC_MATCH, ZK_K_ENC_ENTROPY, ZK_K_ENC_COMPACT, ZK_K_ENC_XXH64, ZK_K_ENC_FSE_BUILD, ZK_K_ENC_DENSE,
        ZK_K_RANGE_PLAN, ZK_K_RANGE_PIECES, ZK_K_RANGE_GATHER, ZK_K_RANGE_STATUS,
-       ZK_K_TRAIN_COUNT, ZK_K_TRAIN_SELECT, ZK_K_TRAIN_STATS, ZK_NKERNELS };
+       ZK_K_TRAIN_COUNT, ZK_K_TRAIN_SELECT, ZK_K_TRAIN_STATS, ZK_K_CDC_MARK, ZK_K_CDC_SELECT, ZK_NKERNELS };
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };
@@ -86,7 +86,9 @@ struct zk_engine {
         zk_devbuf ldm;                      // prefix beyond the matcher's ring: the long-distance table (ZkEncLdm)
         zk_devbuf plan;                     // a frame list planned on the device: the frames' running sums (ZkEncPlanSum, zk_enc_plan_dev.h)
         zk_devbuf train, train_src;         // zk_train_dictionary*: its scratch (zk_train.hip); the host entry point's upload of the samples and their offsets
+        zk_devbuf cdc, cdc_src, cdc_off;    // zk_chunk_boundaries*: a slice's scratch (zk_cdc.hip); the host entry point's upload of a slice, and its offsets
         int plan_choice = 0;                // ZK_CHOICE_ENC_PLAN
+        uint64_t cdc_slice_bytes = 0;       // zk_chunk_boundaries*: input bytes whose candidates are held at a time (0 = 64 MiB), ZK_CHOICE_CDC_SLICE_KIB
         uint64_t train_trial_bytes = 0;     // zk_train_dictionary*: sample bytes the candidates are tried on (0 = 64 MiB), ZK_CHOICE_TRAIN_TRIAL_KIB
         uint64_t dense_slice_bytes = 0;     // input bytes the dense scratch is reserved for (0 = 4 GiB), ZK_CHOICE_ENC_DENSE_SLICE_KIB
         uint64_t dict_slice_bytes = 0;      // dictionary route: bytes of [content tail | frame] records staged at a time (0 = 1 GiB), ZK_CHOICE_ENC_DICT_SLICE_KIB

@@ -123,7 +123,8 @@ class Engine:
 
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
-               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17, "train_trial_kib": 18}
+               "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17, "train_trial_kib": 18,
+               "cdc_slice_kib": 19}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -309,6 +310,81 @@ class Engine:
         if rc != 0:
             self._raise(rc)
         return wr.value
+
+    @staticmethod
+    def _chunk_frames(n, avg_size, min_size):
+        """n / min + 1: no chain has more cuts (the defaults as the library resolves them)"""
+        return n // (min_size or (avg_size or 1 << 21) // 4 or 1) + 1
+
+    def chunk_boundaries(self, data, avg_size=0, min_size=0, max_size=0):
+        """zk_chunk_boundaries: content-defined frame boundaries of `data` (the rule of include/zeekstd_amd.h; 0 = the default).  Returns the
+        count + 1 offsets as an np.uint64 array: what encode_frame_list and the decode calls take."""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        n = int(data.size)
+        par = _lib.ChunkParams(min_size, avg_size, max_size, 0)
+        count = C.c_uint32()
+        cap = self._chunk_frames(n, avg_size, min_size)
+        off = np.zeros(cap + 1, np.uint64)
+        rc = lib.zk_chunk_boundaries(self._h, data.ctypes.data if n else None, n, C.byref(par), off.ctypes.data, cap, C.byref(count))
+        if rc != 0:
+            self._raise(rc)
+        return off[:count.value + 1].copy()
+
+    def chunk_boundaries_dev(self, d_src, n, avg_size=0, min_size=0, max_size=0, stream=None):
+        """zk_chunk_boundaries_dev: the source is a device tensor (or raw pointer); returns a device tensor of count + 1 offsets (int64: the
+        bits of the uint64 array zk_encode_frame_list_dev takes; a view of an array of n / min + 2 entries)."""
+        import torch
+        par = _lib.ChunkParams(min_size, avg_size, max_size, 0)
+        count = C.c_uint32()
+        cap = self._chunk_frames(n, avg_size, min_size)
+        off = torch.zeros(cap + 1, dtype=torch.int64, device=d_src.device if hasattr(d_src, "device") else "cuda")
+        rc = lib.zk_chunk_boundaries_dev(self._h, self._ptr(d_src) if d_src is not None and n else None, n, C.byref(par), off.data_ptr(), cap,
+                                         C.byref(count), stream)
+        if rc != 0:
+            self._raise(rc)
+        return off[:count.value + 1]
+
+    def encode_chunked(self, data, avg_size=0, min_size=0, max_size=0, level=1, checksum=False, prefix=None, dictionary=None):
+        """zk_encode_chunked: content-defined boundaries, then one zstd frame per piece (encode_frame_list on those offsets).  Returns
+        (compressed payload bytes, np.uint64 offsets, np.uint32 c_sizes).  prefix / dictionary as encode_frames."""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        n = int(data.size)
+        if dictionary is not None and prefix:
+            raise ValueError("a prefix and a dictionary exclude each other at this level")
+        par = _lib.ChunkParams(min_size, avg_size, max_size, 0)
+        cap = int(lib.zk_compress_bound_chunked(n, C.byref(par), int(dictionary is not None)))
+        if cap == 0:
+            self._raise(-2003)
+        frames = self._chunk_frames(n, avg_size, min_size)
+        out = np.empty(cap, dtype=np.uint8)
+        off = np.zeros(frames + 1, np.uint64)
+        cs = np.zeros(frames, np.uint32)
+        ds = np.zeros(frames, np.uint32)
+        nfo = C.c_uint32()
+        wr = C.c_uint64()
+        pre = np.frombuffer(bytes(prefix), dtype=np.uint8) if prefix else None
+        rc = lib.zk_encode_chunked(self._h, data.ctypes.data if n else None, n, C.byref(par), level, int(checksum),
+                                   pre.ctypes.data if pre is not None else None, pre.size if pre is not None else 0,
+                                   dictionary._h if dictionary is not None else None, out.ctypes.data, cap, off.ctypes.data, frames,
+                                   cs.ctypes.data, ds.ctypes.data, C.byref(nfo), C.byref(wr))
+        if rc != 0:
+            self._raise(rc)
+        return out[:wr.value].tobytes(), off[:nfo.value + 1].copy(), cs[:nfo.value].copy()
+
+    def encode_chunked_dev(self, d_src, n, d_dst, dst_cap, d_off, off_cap, avg_size=0, min_size=0, max_size=0, level=1, checksum=False,
+                           d_c_sizes=None, d_d_sizes=None, d_prefix=None, prefix_len=0, dictionary=None, stream=None):
+        """zk_encode_chunked_dev: device tensors in and out; d_off receives the offsets (off_cap + 1 uint64 entries), d_c_sizes / d_d_sizes
+        off_cap uint32 entries each.  Returns (frames, bytes written)."""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        par = _lib.ChunkParams(min_size, avg_size, max_size, 0)
+        nfo = C.c_uint32()
+        wr = C.c_uint64()
+        rc = lib.zk_encode_chunked_dev(self._h, opt(d_src), n, C.byref(par), level, int(checksum), opt(d_prefix), prefix_len,
+                                       dictionary._h if dictionary is not None else None, opt(d_dst), dst_cap, opt(d_off), off_cap,
+                                       opt(d_c_sizes), opt(d_d_sizes), C.byref(nfo), C.byref(wr), stream)
+        if rc != 0:
+            self._raise(rc)
+        return nfo.value, wr.value
 
     @staticmethod
     def _train_params(k, d, f, level, dict_id, raw_content):
