@@ -29,7 +29,8 @@ input that misses its edge fails in tests/test_sim_enc_far.py before any kernel 
                        start: no entry at a position whose four bytes are one byte, entries on both sides of it
   launch/KxF           K frames of F bytes (60 000: one segment each, 7 | 8 | 9 | 16 | 24 of them; 2 * ZKE_SEGMENT: 4 | 8): the candidate
                        kernel's XCD remap is live at 8, 16 and 24 workgroups; also cut into slices of one and of three frames
-  launch/last=T        two frames of 60 000 bytes and a last one of T = 1 | 7 | 8 | 30 000 bytes, dense on for the call
+  launch/last=T        two frames of 60 000 bytes and a last one of T = 1 | 7 | 8 | 30 000 bytes, dense on for the call; T = 30 000 also in slices of
+                       60 000 and 90 000 bytes: the engine cuts whole frames while they fit, [0] [1] [2] and [0] [1, 2], not a fixed count per slice
   ldm_frames/...       frames of 300 003 + 70 001, 300 003 + 57 281, 70 001 + 57 281 bytes (a call has one frame size and a last frame): each
                        frame's own zke_ldm_log inside the common stride
   PREFIXES             for zk_k_enc_ldm_build: lengths = 0..3 mod 4, ZKE_WINDOW + 1, and one whose last selected position is n - ZKE_LDM_MIN
@@ -253,7 +254,9 @@ def _launch(k, fs, last=0):
         if last:
             assert refs[k][1] is None if last <= W else refs[k][2]
     name = f"launch/last={last}" if last else f"launch/{k}x{fs}"
-    return Entry(name, bytes(buf), fs, (3,), (0,) if last else (0, fs, 3 * fs), facts)
+    # (last=30000 under slices of 60 000 and 90 000 bytes: frames [0] [1] [2] and [0] [1, 2] -- the short last frame joins the slice before it)
+    slices = (0, fs, 3 * fs) if not last else (0, 60000, 90000) if last == 30000 else (0,)
+    return Entry(name, bytes(buf), fs, (3,), slices, facts)
 
 
 for _k in (7, 8, 9, 16, 24):
@@ -267,7 +270,8 @@ NAMES = list(_B)
 # (name, level, slice bytes) of what tests/sim/enc_far_san.cpp runs under the sanitizers
 SAN_SHAPES = [("frame_start/zeros", 3, 0), ("frame_start/bytes", 3, 0)] + [(f"frame_tail/r{r}", 3, 0) for r in range(4)] + \
     [("frame_tail/zeros/r1", 3, 0), ("seams/t5", 3, 0), ("crowded/text", 3, 0), ("crowded/periodic", 9, 0), ("launch/16x60000", 3, 3 * 60000)] + \
-    [(f"launch/last={t}", 3, 0) for t in (1, 7, 8)]          # (a source that ends 1, 7 and 8 bytes into its last frame: nothing is read behind it)
+    [(f"launch/last={t}", 3, 0) for t in (1, 7, 8)] + \
+    [("launch/last=30000", 3, 90000)]   # (a source that ends 1, 7 and 8 bytes into its last frame: nothing is read behind it; a slice of a frame and a half)
 
 
 @functools.lru_cache(maxsize=None)

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 SIM = os.path.join(ROOT, "tests", "sim")
 CSRC = os.path.join(ROOT, "zeekstd_amd", "csrc")
 DEPS = [os.path.join(SIM, "zk_enc_far_sim.cpp"), os.path.join(SIM, "hip_wg_emu.h")] + \
-       [os.path.join(CSRC, h) for h in ("zk_enc_far.h", "zk_enc_match.h", "zk_enc_plan.h", "zk_enc_device.h", "zk_device.h")]
+       [os.path.join(CSRC, h) for h in ("zk_enc_far.h", "zk_enc_match.h", "zk_enc_sched.h", "zk_enc_plan.h", "zk_enc_device.h", "zk_device.h")]
 _LIB = None
 
 # zk_enc_device.h

@@ -9,17 +9,6 @@
 #include <vector>
 #include "../../zeekstd_amd/csrc/zk_enc_dict.h"
 
-static void zkd_predef(ZkEncTables *t)
-{
-    static const int16_t ll[36] = ZK_LL_DEFNORM, of[29] = ZK_OF_DEFNORM, ml[53] = ZK_ML_DEFNORM;
-    memset(t, 0, sizeof *t);
-    uint8_t sym[512]; int32_t cumul[66];
-    zke_build_ctable(ll, 36, 6, t->ll_state, t->ll_dfs, t->ll_dnb, sym, cumul);
-    zke_build_ctable(of, 29, 5, t->of_state, t->of_dfs, t->of_dnb, sym, cumul);
-    zke_build_ctable(ml, 53, 6, t->ml_state, t->ml_dfs, t->ml_dnb, sym, cumul);
-    t->al[0] = 6; t->al[1] = 5; t->al[2] = 6;
-}
-
 // LSB-first forward bit writer / backward reader over a plain bit vector
 struct ZkdBits {
     std::vector<uint8_t> b;
@@ -48,7 +37,7 @@ int zk_enc_dict_sim_build(const uint8_t *d, size_t n, uint8_t *len_out, uint16_t
     const uint32_t r = zk_dict_parse(d, n, L);
     if (r) return -(int)r;
     if (!L.formatted) return -1;
-    ZkEncTables predef; zkd_predef(&predef);
+    ZkEncTables predef; zk_build_enc_tables(&predef);
     std::vector<ZkEncDictDev> dev(1);
     const uint32_t r2 = zke_dict_build(d, L, predef, &dev[0]);
     if (r2) return -(int)r2;

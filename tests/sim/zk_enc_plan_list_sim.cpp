@@ -1,13 +1,12 @@
 // zk_enc_plan_list_sim.cpp -- TEST HARNESS (never shipped, never linked into libzeekstd_amd.so).
 // An encode over a caller-given frame list (zk_encode_frame_list*) on the CPU: the list forms of the plan (zk_enc_plan.h), the plan kernels
 // (zk_enc_plan_dev.h), the far-history kernels (zk_enc_far.h) and the match kernel (zk_enc_match.h) -- the very sources hipcc compiles --
-// one workgroup at a time under the fiber emulator of hip_wg_emu.h, with the launchers' grids and the engine's slices (zk_engine_enc.hip:
-// zk_enc_far_history, zk_enc_match).  tests/test_enc_plan_list.py compares what they leave with the host plan, record by record, and with the
-// CPU twin frame by frame; tests/sim/enc_plan_list_san.cpp runs the same under AddressSanitizer + UBSan.  Every buffer a kernel sees is a
-// heap allocation of EXACTLY the engine's size, poisoned first.
-#include "hip_wg_emu.h"
+// one workgroup at a time under the fiber emulator of hip_wg_emu.h, with the launchers' grids, the engine's slices and its buffer sizes out of
+// the functions zk_enc_far_history and zk_enc_match call themselves (zk_enc_sched.h).  tests/test_enc_plan_list.py compares what they leave
+// with the host plan, record by record, and with the CPU twin frame by frame; tests/sim/enc_plan_list_san.cpp runs the same under
+// AddressSanitizer + UBSan.  Every buffer a kernel sees is a heap allocation of EXACTLY the engine's size, poisoned first.
+#include "zk_enc_match_emu.h"
 #include "../../zeekstd_amd/csrc/zk_enc_far.h"
-#include "../../zeekstd_amd/csrc/zk_enc_match2.h"
 #include "../../zeekstd_amd/csrc/zk_enc_plan_dev.h"
 #include <memory>
 
@@ -119,50 +118,38 @@ extern "C" int zk_plan_list_sim_encode(const uint8_t *src_in, const uint64_t *of
     const ZkEncPlan &pl = p.pl;
     const uint64_t n = off[count] - off[0];
     if (pl.nb > blk_cap || pl.seq_total + 1 > seq_cap || n > lit_cap) return -1;
-    uint64_t frame_max = 0;
+    uint32_t frame_max = 1;                     // (what the entry point hands on as frame_size: the largest frame, at least 1)
     for (uint32_t f = 0; f < count; f++) if (p.frames[f].d_size > frame_max) frame_max = p.frames[f].d_size;
+    const ZkEncCut cut = {off, count, n, frame_max};
+    const ZkEncFarPlan fp = zk_enc_far_plan(cut, level, 0, 0, pl.nseg, slice_bytes);
     const auto src = zkl_exact<uint8_t>(n);
     if (n) memcpy(src.get(), src_in + off[0], n);
-    ZkEncLdm ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0, nullptr, 0, 0};
+    ZkEncLdm ldm = fp.ldm;
     std::unique_ptr<ZkEncLdmFrame[]> lf;
     std::unique_ptr<uint32_t[]> table, cand, part, poff;
-    size_t span = 0, ncand = 0;
-    uint64_t slice_cap = 0;
+    const size_t ncand = fp.cand_words;
     *nlf_out = 0;
     emu_set_lane_order(descending != 0);
-    if (zke_ldm_in_frame(level, 0, frame_max)) {
-        // zk_enc_far_history, list branch: a record and 2^zke_ldm_log(size) entries per frame that qualifies, behind the shared empty table
-        ldm.inframe = 1; ldm.frame_size = (uint32_t)frame_max; ldm.n_total = n; ldm.log = zke_ldm_log(frame_max);
-        uint32_t nlf = 0;
-        for (uint32_t f = 0; f < count; f++) nlf += zke_ldm_in_frame(level, 0, p.frames[f].d_size);
+    if (fp.kind == ZK_ENC_FAR_INFRAME) {
+        const uint32_t nlf = ldm.nlf;
+        if (nlf > lf_cap || fp.entries > table_cap) { emu_set_lane_order(false); return -1; }
         lf = zkl_exact<ZkEncLdmFrame>(nlf);
-        uint64_t entries = zke_ldm_list_shared();
-        for (uint32_t f = 0, k = 0; f < count; f++) if (zke_ldm_in_frame(level, 0, p.frames[f].d_size)) {
-            lf[k++] = ZkEncLdmFrame{p.frames[f].src_off, entries, p.frames[f].d_size, 0};
-            entries += 1ull << zke_ldm_log(p.frames[f].d_size);
+        zk_enc_far_list_frames(cut, level, 0, lf.get());
+        table = zkl_exact<uint32_t>((size_t)fp.entries);
+        memset(table.get(), 0xFF, fp.table_bytes);
+        ldm.lf = lf.get();
+        for (uint32_t f0 = 0; f0 < nlf; f0 += ZK_ENC_GRID_Y_MAX) {
+            const uint32_t gx = fp.build_gx, cnt = zk_enc_ldm_frames_gy(nlf, f0);
+            for (uint32_t by = 0; by < cnt; by++)
+                for (uint32_t bx = 0; bx < gx; bx++)
+                    emu_run_workgroup(256, bx, [&]() { zk_k_enc_ldm_build_frames(src.get(), ldm, table.get(), f0); }, gx, by, cnt);
         }
-        if (nlf > lf_cap || entries > table_cap) { emu_set_lane_order(false); return -1; }
-        table = zkl_exact<uint32_t>(entries);
-        memset(table.get(), 0xFF, entries * sizeof(uint32_t));
-        ldm.lf = lf.get(); ldm.nlf = nlf;
-        // zk_launch_enc_ldm_build_frames, list form: "wgs = (list_max + 4095) / 4096", "dim3(wgs < 1024 ? wgs : 1024, cnt)", f0 in steps of 65535
-        const uint64_t wgs = (frame_max + 4095) / 4096;
-        const uint32_t gx = (uint32_t)(wgs < 1024 ? wgs : 1024);
-        for (uint32_t by = 0; by < nlf; by++)
-            for (uint32_t bx = 0; bx < gx; bx++)
-                emu_run_workgroup(256, bx, [&]() { zk_k_enc_ldm_build_frames(src.get(), ldm, table.get(), 0); }, gx, by, nlf);
         ldm.table = table.get();
         for (uint32_t k = 0; k < nlf; k++) { lf_out[3 * k] = lf[k].start; lf_out[3 * k + 1] = lf[k].tbase; lf_out[3 * k + 2] = lf[k].size; }
         *nlf_out = nlf;
-        memcpy(table_out, table.get(), entries * sizeof(uint32_t));
-        if (zke_dense_in_frame(level, 0, frame_max)) {
-            ldm.dlog = zke_dense_log(level);
-            const uint64_t dense_slice = slice_bytes ? slice_bytes : 4ull << 30;
-            slice_cap = dense_slice > frame_max ? dense_slice : frame_max;
-            span = (size_t)(n < slice_cap ? n : slice_cap);
-            if (slice_cap >= n) slice_cap = 0;
-            ncand = span + ZKE_DENSE_SLACK;
-            cand = zkl_exact<uint32_t>(ncand); part = zkl_exact<uint32_t>(ncand); poff = zkl_exact<uint32_t>((size_t)pl.nseg * (ZKD_NBMAX + 1));
+        memcpy(table_out, table.get(), fp.table_bytes);
+        if (fp.dense_span) {
+            cand = zkl_exact<uint32_t>(ncand); part = zkl_exact<uint32_t>(ncand); poff = zkl_exact<uint32_t>(fp.poff_words);
             ldm.dense = cand.get();
         }
     }
@@ -170,13 +157,10 @@ extern "C" int zk_plan_list_sim_encode(const uint8_t *src_in, const uint64_t *of
     const auto seqs = zkl_exact<uint64_t>(pl.seq_total + 1);
     const auto lits = zkl_exact<uint8_t>(n + 64);
     int rc = (int)pl.nb;
-    // zk_enc_match: whole frames while they fit in slice_cap bytes, never less than one
-    for (uint32_t f0 = 0, s0 = 0, f1, s1; f0 < count; f0 = f1, s0 = s1) {
-        f1 = count; s1 = pl.nseg;
-        if (slice_cap)
-            for (f1 = f0, s1 = s0; f1 < count && (f1 == f0 || p.doff[f1 + 1] - p.doff[f0] <= slice_cap); f1++) s1 += (p.frames[f1].d_size + ZKE_SEGMENT - 1) / ZKE_SEGMENT;
-        const uint64_t lo = p.doff[f0], hi = p.doff[f1];
-        const uint32_t nsegs = s1 - s0;
+    for (uint32_t f0 = 0, s0 = 0; f0 < count;) {
+        const ZkEncSlice end = zk_enc_slice_end(cut, 0, n, fp.slice_cap, pl.nseg, f0, s0);
+        const uint64_t lo = p.doff[f0], hi = p.doff[end.f1];
+        const uint32_t nsegs = end.s1 - s0;
         const ZkEncFrame *sg = p.segs.data() + s0;
         ZkEncLdm sl = ldm;
         if (sl.dense && nsegs) {
@@ -189,32 +173,12 @@ extern "C" int zk_plan_list_sim_encode(const uint8_t *src_in, const uint64_t *of
             memcpy(cand_out + lo, cand.get(), (size_t)(hi - lo) * sizeof(uint32_t));
             for (size_t i = (size_t)(hi - lo); i < ncand; i++) if (cand[i] != ZKL_POISON || part[i] != ZKL_POISON) rc = -2;
         }
-        if (!with_match) continue;
-        for (uint32_t b = 0; b < nsegs; b++) {
-            auto run = [&]() {
-                // zk_launch_enc_match
-                if (sl.dense) {
-                    if (zke_step(level) == 1024) zk_k_enc_match<15, 1, 1024, true, true>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get(), sl);
-                    else zk_k_enc_match<15, 1, 4096, true, true>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get(), sl);
-                }
-                else if (sl.table) {
-                    if (zke_fast(level)) zk_k_enc_match<14, 0, 4096, true>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get(), sl);
-                    else if (zke_step(level) == 1024) zk_k_enc_match<15, 1, 1024, true>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get(), sl);
-                    else zk_k_enc_match<15, 1, 4096, true>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get(), sl);
-                }
-                else if (zke_fast(level)) zk_k_enc_match2<14>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get());
-                else if (zke_step(level) == 1024) zk_k_enc_match<15, 1, 1024, false>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get(), sl);
-                else zk_k_enc_match<15, 1, 4096, false>(src.get(), sg, p.blocks.data(), seqs.get(), lits.get(), sl);
-            };
-            emu_run_workgroup(ZKE_THREADS, b, run, nsegs);
-        }
+        if (with_match) zk_emu_enc_match(src.get(), sg, nsegs, p.blocks.data(), seqs.get(), lits.get(), level, sl);
+        f0 = end.f1; s0 = end.s1;
     }
     emu_set_lane_order(false);
     if (with_match) {
-        for (uint32_t b = 0; b < pl.nb; b++) {
-            blk_nseq[b] = p.blocks[b].nseq; blk_nlit[b] = p.blocks[b].nlit; blk_bsz[b] = p.blocks[b].bsz;
-            seq_at[b] = p.blocks[b].seq_base; lit_at[b] = p.blocks[b].lit_base;
-        }
+        zk_emu_enc_blocks_out(p.blocks.data(), pl.nb, blk_nseq, blk_nlit, blk_bsz, seq_at, lit_at);
         memcpy(seqs_out, seqs.get(), (size_t)(pl.seq_total + 1) * 8);
         memcpy(lits_out, lits.get(), (size_t)n);
     }

@@ -1,12 +1,9 @@
 // zk_enc_sim.cpp -- TEST HARNESS (never shipped, never linked into libzeekstd_amd.so).
 // Runs the encoder's match + parse kernel (zeekstd_amd/csrc/zk_enc_match.h, the very source hipcc compiles for gfx950)
 // on the CPU, one workgroup at a time, under the fiber emulator of hip_wg_emu.h, with the frame / block / segment plan the
-// engine uses (zk_enc_plan.h).  The -m "not gpu" suite compares its sequences and literals with the CPU twin
-// (oracle/zstd_oracle_enc.c) block by block -- the kernel's logic is checked before a GPU is involved.
-#include "hip_wg_emu.h"
-#include "../../zeekstd_amd/csrc/zk_enc_match.h"
-#include "../../zeekstd_amd/csrc/zk_enc_match2.h"
-#include "../../zeekstd_amd/csrc/zk_enc_plan.h"
+// engine uses (zk_enc_plan.h), the far history and the kernel instance it picks (zk_enc_sched.h).  The -m "not gpu" suite
+// compares its sequences and literals with the CPU twin (oracle/zstd_oracle_enc.c) block by block -- the kernel's logic is checked before a GPU is involved.
+#include "zk_enc_match_emu.h"
 
 // Encode plan + match kernel over src[0, n) cut into frames of frame_size bytes; prefix (may be null) is what
 // zk_encode_frames_prefix references.  Outputs, per block b (in plan order): blk_nseq[b], blk_nlit[b], blk_bsz[b]; the
@@ -37,14 +34,14 @@ extern "C" int zk_enc_sim_match(const uint8_t *src, uint64_t n, uint32_t frame_s
     }
     // long-distance table over the prefix (the engine builds it with zk_k_enc_ldm_build; here sequentially, same rule -- the kernel itself is
     // held to that rule by tests/test_sim_enc_far.py::test_sampled_table_over_a_prefix_equals_twin)
-    ZkEncLdm ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0};
+    const ZkEncFarPlan far = zk_enc_far_plan(ZkEncCut{nullptr, pl.nf, n, frame_size}, level, prefix ? prefix_len : 0, hist, pl.nseg, 0);
+    ZkEncLdm ldm = far.ldm;
     std::vector<uint32_t> table, dense;
     std::vector<uint8_t> pcopy;
-    if (!prefix && zke_ldm_in_frame(level, 0, frame_size < n ? frame_size : n)) {
+    if (far.kind == ZK_ENC_FAR_INFRAME) {
         // in-frame far history: one table per frame over its own bytes (the engine: zk_k_enc_ldm_build_frames; here sequentially, same rule --
         // the kernel itself is held to it by tests/test_sim_enc_far.py::test_sampled_tables_per_frame_equal_twin)
-        ldm.inframe = 1; ldm.frame_size = frame_size; ldm.n_total = n; ldm.log = zke_ldm_log(frame_size < n ? frame_size : n);
-        table.assign((size_t)pl.nf << ldm.log, ZKE_LDM_NONE);
+        table.assign((size_t)far.entries, ZKE_LDM_NONE);
         for (uint32_t f = 0; f < pl.nf; f++) {
             const uint64_t at = (uint64_t)f * frame_size, fsz = n - at < frame_size ? n - at : frame_size;
             const uint32_t log = zke_ldm_log(fsz);
@@ -57,12 +54,11 @@ extern "C" int zk_enc_sim_match(const uint8_t *src, uint64_t n, uint32_t frame_s
             }
         }
         ldm.table = table.data();
-        if (zke_dense_in_frame(level, 0, frame_size < n ? frame_size : n)) {
+        if (far.dense_span) {
             // dense far history: every position's far candidate out of the first / last occurrence per slot and segment (the engine:
             // zk_k_enc_dense_cand; here sequentially, same rule -- the kernels themselves are held to it by
             // tests/test_sim_enc_far.py::test_dense_candidates_equal_twin)
-            ldm.dlog = zke_dense_log(level);
-            dense.assign((size_t)n + ZKE_DENSE_SLACK, 0);
+            dense.assign((size_t)n + ZKE_DENSE_SLACK, 0);          // (one slice: indexed like the source)
             const size_t slots = (size_t)1 << ldm.dlog;
             std::vector<uint32_t> first(slots), last(slots), prev(slots);
             auto h5 = [&](const uint8_t *p) { uint32_t lo; memcpy(&lo, p, 4); return zke_hash(lo, p[4], ldm.dlog); };
@@ -98,13 +94,12 @@ extern "C" int zk_enc_sim_match(const uint8_t *src, uint64_t n, uint32_t frame_s
             ldm.dense = dense.data();
         }
     }
-    if (prefix && prefix_len > ZKE_WINDOW) {
-        const uint64_t usable = zke_ldm_usable(prefix_len);
-        ldm.plen = prefix_len; ldm.u0 = prefix_len - usable; ldm.log = zke_ldm_log(usable);
+    if (far.kind == ZK_ENC_FAR_PREFIX) {
+        const uint64_t usable = ldm.plen - ldm.u0;
         pcopy.assign(16 + usable + ZKE_LDM_SLACK, 0);                 // what the engine keeps on the device: slack | prefix[u0, plen) | slack
         memcpy(pcopy.data() + 16, prefix + ldm.u0, usable);
         ldm.pfx = pcopy.data() + 16 - ldm.u0;
-        table.assign((size_t)1 << ldm.log, ZKE_LDM_NONE);
+        table.assign((size_t)far.entries, ZKE_LDM_NONE);
         for (uint64_t i = 0; i + ZKE_LDM_MIN <= usable; i++) {
             uint32_t w[4]; memcpy(w, pcopy.data() + 16 + i, 16);
             const uint32_t h = zke_ldm_hash(w[0], w[1], w[2], w[3]);
@@ -114,27 +109,8 @@ extern "C" int zk_enc_sim_match(const uint8_t *src, uint64_t n, uint32_t frame_s
         }
         ldm.table = table.data();
     }
-    for (uint32_t s = 0; s < pl.nseg; s++) {
-        auto run = [&]() {
-            if (ldm.dense) {
-                if (zke_step(level) == 1024) zk_k_enc_match<15, 1, 1024, true, true>(msrc, segs.data(), blocks.data(), seqs, lits, ldm);
-                else zk_k_enc_match<15, 1, 4096, true, true>(msrc, segs.data(), blocks.data(), seqs, lits, ldm);
-            }
-            else if (ldm.table) {
-                if (zke_fast(level)) zk_k_enc_match<14, 0, 4096, true>(msrc, segs.data(), blocks.data(), seqs, lits, ldm);
-                else if (zke_step(level) == 1024) zk_k_enc_match<15, 1, 1024, true>(msrc, segs.data(), blocks.data(), seqs, lits, ldm);
-                else zk_k_enc_match<15, 1, 4096, true>(msrc, segs.data(), blocks.data(), seqs, lits, ldm);
-            }
-            else if (zke_fast(level)) zk_k_enc_match2<14>(msrc, segs.data(), blocks.data(), seqs, lits);
-            else if (zke_step(level) == 1024) zk_k_enc_match<15, 1, 1024, false>(msrc, segs.data(), blocks.data(), seqs, lits, ldm);
-            else zk_k_enc_match<15, 1, 4096, false>(msrc, segs.data(), blocks.data(), seqs, lits, ldm);
-        };
-        emu_run_workgroup(ZKE_THREADS, s, run);
-    }
-    for (uint32_t b = 0; b < pl.nb; b++) {
-        blk_nseq[b] = blocks[b].nseq; blk_nlit[b] = blocks[b].nlit; blk_bsz[b] = blocks[b].bsz;
-        seq_at[b] = blocks[b].seq_base; lit_at[b] = blocks[b].lit_base;
-    }
+    zk_emu_enc_match(msrc, segs.data(), pl.nseg, blocks.data(), seqs, lits, level, ldm);
+    zk_emu_enc_blocks_out(blocks.data(), pl.nb, blk_nseq, blk_nlit, blk_bsz, seq_at, lit_at);
     return (int)pl.nb;
 }
 

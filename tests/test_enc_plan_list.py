@@ -16,8 +16,8 @@ from oracle import zko
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM = os.path.join(ROOT, "tests", "sim")
 CSRC = os.path.join(ROOT, "zeekstd_amd", "csrc")
-DEPS = [os.path.join(SIM, "zk_enc_plan_list_sim.cpp"), os.path.join(SIM, "hip_wg_emu.h")] + \
-       [os.path.join(CSRC, h) for h in ("zk_enc_plan_dev.h", "zk_enc_plan.h", "zk_enc_far.h", "zk_enc_match.h", "zk_enc_match2.h", "zk_enc_device.h", "zk_device.h")]
+DEPS = [os.path.join(SIM, "zk_enc_plan_list_sim.cpp"), os.path.join(SIM, "hip_wg_emu.h"), os.path.join(SIM, "zk_enc_match_emu.h")] + \
+       [os.path.join(CSRC, h) for h in ("zk_enc_plan_dev.h", "zk_enc_plan.h", "zk_enc_sched.h", "zk_enc_far.h", "zk_enc_match.h", "zk_enc_match2.h", "zk_enc_device.h", "zk_device.h")]
 WINDOW, SEGMENT, LDM_NONE = E.WINDOW, E.SEGMENT, 0xFFFFFFFF
 _LIB = None
 P = C.c_void_p

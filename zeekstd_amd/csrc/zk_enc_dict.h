@@ -192,6 +192,21 @@ static inline void zke_predef_costs(uint32_t cost[3][64])
     }
 }
 
+// The predefined FSE compression tables (host, once per engine): what every frame starts from, and what zke_dict_build takes its value tables from.
+static inline void zk_build_enc_tables(ZkEncTables *t)
+{
+    static const int16_t ll[36] = ZK_LL_DEFNORM, of[29] = ZK_OF_DEFNORM, ml[53] = ZK_ML_DEFNORM;
+    static const uint32_t llv[36] = ZK_LL_TABLE, mlv[53] = ZK_ML_TABLE;
+    memset(t, 0, sizeof *t);
+    uint8_t sym[512]; int32_t cumul[66];
+    zke_build_ctable(ll, 36, 6, t->ll_state, t->ll_dfs, t->ll_dnb, sym, cumul);
+    zke_build_ctable(of, 29, 5, t->of_state, t->of_dfs, t->of_dnb, sym, cumul);
+    zke_build_ctable(ml, 53, 6, t->ml_state, t->ml_dfs, t->ml_dnb, sym, cumul);
+    for (int i = 0; i < 36; i++) t->ll_val[i] = llv[i];
+    for (int i = 0; i < 53; i++) t->ml_val[i] = mlv[i];
+    t->al[0] = 6; t->al[1] = 5; t->al[2] = 6;
+}
+
 // The compression side of a formatted dictionary's four tables.  `predef` supplies the value tables (ll_val / ml_val), which are the same
 // in every set.  0, or ZK_E_DICT_CORRUPTED (what zk_dict_create refuses too).
 static inline uint32_t zke_dict_build(const uint8_t *d, const ZkDictLayout &L, const ZkEncTables &predef, ZkEncDictDev *out)

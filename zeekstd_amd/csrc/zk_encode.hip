@@ -44,6 +44,7 @@ extern "C" void zk_debug_enc_clocks(unsigned long long *out, int reset)
 #include "zk_enc_match2.h"
 #include "zk_enc_far.h"
 #include "zk_enc_plan_dev.h"
+#include "zk_enc_sched.h"
 #ifdef ZKE_ENT_CLOCKS
 // experiments: the same for the entropy kernel (per wave: slot = 4 * phase + wave; tools/ent_clocks.py)
 __device__ unsigned long long zke_dbg_clk[48];
@@ -1031,44 +1032,30 @@ void zk_launch_enc_dense_cand(hipStream_t st, const uint8_t *src, const ZkEncFra
     hipLaunchKernelGGL(zk_k_enc_dense_cand, dim3(nsegs), dim3(1024), 0, st, src, segs, ldm, (const uint32_t *)part, (const uint32_t *)poff, cand);
 }
 // (both return the HIP verdict of clearing the table: a table that was not cleared holds an earlier call's positions, and the matcher
-//  would follow them -- ADVICE r4 / r5)
-// (a frame list: nframes = the frames with a table, ldm.lf; list_entries = all their entries + the shared empty ones, list_max = the largest such frame)
-int zk_launch_enc_ldm_build_frames(hipStream_t st, const uint8_t *src, const ZkEncLdm &ldm, uint32_t *table, uint32_t nframes, uint64_t list_entries, uint32_t list_max)
+//  would follow them -- ADVICE r4 / r5.  table_bytes, gx: ZkEncFarPlan's table_bytes and build_gx)
+// (a frame list: nframes = the frames with a table, ldm.lf)
+int zk_launch_enc_ldm_build_frames(hipStream_t st, const uint8_t *src, const ZkEncLdm &ldm, uint32_t *table, uint32_t nframes, size_t table_bytes, uint32_t gx)
 {
-    if (hipMemsetAsync(table, 0xFF, ldm.lf ? (size_t)list_entries * sizeof(uint32_t) : ((size_t)nframes * sizeof(uint32_t)) << ldm.log, st) != hipSuccess) return -1;
-    const uint64_t wgs = ((uint64_t)(ldm.lf ? list_max : ldm.frame_size) + 4095) / 4096;
-    // a grid's y dimension ends at 65535 (4 GiB of 64 KiB frames are 65536 of them): frames in launches of at most that many
-    for (uint32_t f0 = 0; f0 < nframes; f0 += 65535u) {
-        const uint32_t cnt = nframes - f0 < 65535u ? nframes - f0 : 65535u;
-        hipLaunchKernelGGL(zk_k_enc_ldm_build_frames, dim3((uint32_t)(wgs < 1024 ? wgs : 1024), cnt), dim3(256), 0, st, src, ldm, table, f0);
-    }
+    if (hipMemsetAsync(table, 0xFF, table_bytes, st) != hipSuccess) return -1;
+    for (uint32_t f0 = 0; f0 < nframes; f0 += ZK_ENC_GRID_Y_MAX)
+        hipLaunchKernelGGL(zk_k_enc_ldm_build_frames, dim3(gx, zk_enc_ldm_frames_gy(nframes, f0)), dim3(256), 0, st, src, ldm, table, f0);
     return 0;
 }
-int zk_launch_enc_ldm_build(hipStream_t st, const ZkEncLdm &ldm, uint32_t *table)
+int zk_launch_enc_ldm_build(hipStream_t st, const ZkEncLdm &ldm, uint32_t *table, size_t table_bytes, uint32_t gx)
 {
-    if (hipMemsetAsync(table, 0xFF, sizeof(uint32_t) << ldm.log, st) != hipSuccess) return -1;
-    const uint64_t n = ldm.plen - ldm.u0, wgs = (n + 1023) / 1024;
-    hipLaunchKernelGGL(zk_k_enc_ldm_build, dim3((uint32_t)(wgs < 4096 ? wgs : 4096)), dim3(256), 0, st, ldm, table);
+    if (hipMemsetAsync(table, 0xFF, table_bytes, st) != hipSuccess) return -1;
+    hipLaunchKernelGGL(zk_k_enc_ldm_build, dim3(gx), dim3(256), 0, st, ldm, table);
     return 0;
 }
 void zk_launch_enc_match(hipStream_t st, const uint8_t *src, const ZkEncFrame *segs, uint32_t nsegs, ZkEncBlock *blocks, uint64_t *seqs, uint8_t *lits, int level, const ZkEncLdm &ldm)
 {
     if (!nsegs) return;
-    // one instance per setting of zk_enc_device.h (zke_hash_log / zke_lazy / zke_step), with and without long-distance matching
-#define ZKE_GO(H, L, S, D) hipLaunchKernelGGL((zk_k_enc_match<H, L, S, D>), dim3(nsegs), dim3(ZKE_THREADS), 0, st, src, segs, blocks, seqs, lits, ldm)
-    if (ldm.dense) {                                            // (level 0 / >= 3 in frame: never the fast setting)
-        if (zke_step(level) == 1024) hipLaunchKernelGGL((zk_k_enc_match<15, 1, 1024, true, true>), dim3(nsegs), dim3(ZKE_THREADS), 0, st, src, segs, blocks, seqs, lits, ldm);
-        else hipLaunchKernelGGL((zk_k_enc_match<15, 1, 4096, true, true>), dim3(nsegs), dim3(ZKE_THREADS), 0, st, src, segs, blocks, seqs, lits, ldm);
-    }
-    else if (ldm.table) {
-        if (zke_fast(level)) ZKE_GO(14, 0, 4096, true);
-        else if (zke_step(level) == 1024) ZKE_GO(15, 1, 1024, true);
-        else ZKE_GO(15, 1, 4096, true);
-    }
-    else if (zke_fast(level)) hipLaunchKernelGGL((zk_k_enc_match2<14>), dim3(nsegs), dim3(ZKE_THREADS), 0, st, src, segs, blocks, seqs, lits);   // zke_fast2(): the plan set minmatch 5
-    else if (zke_step(level) == 1024) ZKE_GO(15, 1, 1024, false);
-    else ZKE_GO(15, 1, 4096, false);
+    switch (zk_enc_match_kernel(level, ldm.table != nullptr, ldm.dense != nullptr)) {
+#define ZKE_GO(name, kernel, takes_ldm) \
+    case name: hipLaunchKernelGGL(kernel, dim3(nsegs), dim3(ZKE_THREADS), 0, st, src, segs, blocks, seqs, lits ZK_ENC_MATCH_LDM_##takes_ldm(ldm)); break;
+    ZK_ENC_MATCH_KERNELS(ZKE_GO)
 #undef ZKE_GO
+    }
 }
 void zk_launch_enc_fse_build(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
                              const ZkEncTables *predef, ZkEncTables *ftab, const ZkEncDictDev *dd)

@@ -6,23 +6,9 @@
 #include "zk_engine.h"
 #include "zk_kernels.h"
 #include "zk_enc_plan.h"
+#include "zk_enc_sched.h"
 #include "zk_enc_dict.h"
 #include "zk_dict.h"
-
-// ---------------------------------------------------------------- predefined FSE compression tables (host, once)
-void zk_build_enc_tables(ZkEncTables *t)
-{
-    static const int16_t ll[36] = ZK_LL_DEFNORM, of[29] = ZK_OF_DEFNORM, ml[53] = ZK_ML_DEFNORM;
-    static const uint32_t llv[36] = ZK_LL_TABLE, mlv[53] = ZK_ML_TABLE;
-    memset(t, 0, sizeof *t);
-    uint8_t sym[512]; int32_t cumul[66];
-    zke_build_ctable(ll, 36, 6, t->ll_state, t->ll_dfs, t->ll_dnb, sym, cumul);
-    zke_build_ctable(of, 29, 5, t->of_state, t->of_dfs, t->of_dnb, sym, cumul);
-    zke_build_ctable(ml, 53, 6, t->ml_state, t->ml_dfs, t->ml_dnb, sym, cumul);
-    for (int i = 0; i < 36; i++) t->ll_val[i] = llv[i];
-    for (int i = 0; i < 53; i++) t->ml_val[i] = mlv[i];
-    t->al[0] = 6; t->al[1] = 5; t->al[2] = 6;
-}
 
 // Per frame: header (6) + checksum (4) + a 3-byte header for more blocks than a frame can have.  A frame has one block up to 4 KiB and blocks
 // of at least 4 KiB above that (zke_block_max), so ceil(frame_size / 1024) + 8 leaves at least 8 block headers (24 bytes) spare, and three per
@@ -82,6 +68,7 @@ extern "C" int zk_encode_frames_dev(zk_engine *e, const void *d_src, uint64_t n,
 namespace {
 struct ZkEncLayout {
     ZkEncPlan pl;
+    ZkEncCut cut;                           // the call's frames, from the arguments alone (zk_enc_sched.h)
     // pinned (zk_engine::Enc::pin), rounded to 64 bytes each: frames | blocks (+ 1) | doff | the predefined tables | segs
     ZkEncFrame *frames; ZkEncBlock *blocks; uint64_t *doff; ZkEncTables *htab; ZkEncFrame *segs;
     size_t frames_bytes;                    // of the frame list, rounded: the block list follows it on both sides, so one copy uploads both
@@ -105,20 +92,6 @@ struct ZkEncLayout {
     const ZkEncDictDev *dd;                 // a formatted dictionary's tables, or null
     ZkEncDictId did; const ZkEncDictId *pdid;   // the Dictionary_ID field (pdid: null on every other route and for a raw-content dictionary)
 };
-// where frame f starts in the source, its bytes, and where its record starts in the matcher's source -- host arithmetic from the arguments alone
-// (what zke_plan_frame is handed), so that nothing on the host reads the frame records: they may have been made on the device
-inline uint64_t zk_enc_frame_src(const zk_enc_args &a, uint32_t f) { return a.list ? a.list[f] - a.list[0] : (uint64_t)f * a.frame_size; }
-inline uint32_t zk_enc_frame_bytes(const zk_enc_args &a, uint32_t f)
-{
-    if (a.list) return (uint32_t)(a.list[f + 1] - a.list[f]);
-    const uint64_t at = (uint64_t)f * a.frame_size;
-    return (uint32_t)(a.n - at < a.frame_size ? a.n - at : a.frame_size);
-}
-inline uint64_t zk_enc_frame_rec(const zk_enc_args &a, uint32_t hist, uint32_t f)
-{
-    if (!hist) return zk_enc_frame_src(a, f);
-    return a.list ? (uint64_t)f * hist + zk_enc_frame_src(a, f) : (uint64_t)f * ((uint64_t)hist + a.frame_size);
-}
 template <class T> int zk_enc_reserve(zk_engine *e, zk_devbuf &b, size_t bytes, T **p)
 {
     const int rc = zk_devbuf_reserve(e, b, bytes);
@@ -185,6 +158,7 @@ static int zk_enc_plan_upload(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
         L.pl = ZkEncPlan{a.list_count, t.nb, t.nseg, hist, t.seq, t.scratch};
     }
     else if (!(a.list ? zke_plan_count_list(a.list, a.list_count, hist, &L.pl) : zke_plan_count(a.n, a.frame_size, hist, &L.pl))) return -(int)ZK_E_GENERIC;
+    L.cut = ZkEncCut{a.list, L.pl.nf, a.n, a.frame_size};
     int rc;
     if ((rc = zk_enc_layout(e, a, L))) return rc;
     if (!e->enc.tables_ready) { zk_build_enc_tables(&e->enc.tables); e->enc.tables_ready = true; }
@@ -209,110 +183,78 @@ static int zk_enc_plan_upload(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L
 static int zk_enc_stage_hist(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
     const uint32_t hist = L.pl.hist;
-    // all the records: as many as frames, one behind the other (a list's are as long as its frames)
-    const uint64_t rec_total = a.list ? (uint64_t)L.pl.nf * hist + a.n : (uint64_t)L.pl.nf * ((uint64_t)hist + a.frame_size);
-    L.rec_total = hist ? rec_total : a.n;
-    if (hist && a.cdict) {
-        // the dictionary route: a bounded buffer for slices of whole frames, staged by zk_enc_match right before each slice is matched
-        const uint64_t rec = (uint64_t)hist + a.frame_size, cap = e->enc.dict_slice_bytes ? e->enc.dict_slice_bytes : 1ull << 30;
-        L.slice_cap = cap > rec ? cap : rec;
-        int rc;
-        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)(L.slice_cap < rec_total ? L.slice_cap : rec_total) + 64, &L.stage))) return rc;
-        if (L.slice_cap >= rec_total) L.slice_cap = 0;
-    } else if (hist) {
+    const ZkEncStagePlan p = zk_enc_stage_plan(L.cut, hist, a.cdict != nullptr, e->enc.dict_slice_bytes);
+    L.rec_total = p.rec_total;
+    if (hist) {
         uint8_t *stage;
         int rc;
-        if ((rc = zk_enc_reserve(e, e->enc.hist, (size_t)rec_total + 64, &stage))) return rc;
-        zk_launch_enc_stage_hist(st, L.src, (const uint8_t *)a.d_prefix + (a.prefix_len - hist), L.d_frames, L.pl.nf, stage);
-        L.msrc = stage;
+        if ((rc = zk_enc_reserve(e, e->enc.hist, p.stage_bytes + 64, &stage))) return rc;
+        // the dictionary route: slices of whole frames, staged by zk_enc_match right before each slice is matched
+        if (a.cdict) { L.stage = stage; L.slice_cap = p.slice_cap; }
+        else {
+            zk_launch_enc_stage_hist(st, L.src, (const uint8_t *)a.d_prefix + (a.prefix_len - hist), L.d_frames, L.pl.nf, stage);
+            L.msrc = stage;
+        }
     }
     if (L.segs) ZK_HIP(hipMemcpyAsync(L.d_segs, L.segs, (size_t)L.pl.nseg * sizeof(ZkEncFrame), hipMemcpyHostToDevice, st));
     return 0;
 }
 
 // far history (ZkEncLdm), one of: none; a table per frame over its own bytes, with the dense candidates on top at the dense
-// levels; a table over a prefix the ring cannot hold (rebuilt per call: the bytes are the caller's)
+// levels; a table over a prefix the ring cannot hold (rebuilt per call: the bytes are the caller's) -- zk_enc_far_plan says which
 static int zk_enc_far_history(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
-    const uint32_t frame_size = a.frame_size, nf = L.pl.nf;
+    const uint64_t plen = a.d_prefix ? a.prefix_len : 0;
+    const ZkEncFarPlan p = zk_enc_far_plan(L.cut, a.level, plen, L.pl.hist, L.pl.nseg, e->enc.dense_slice_bytes);
     ZkEncLdm &ldm = L.ldm;
-    ldm = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0, nullptr, 0, 0};
-    L.dense_span = 0;
+    ldm = p.ldm;
+    L.dense_span = p.dense_span;
     int rc;
     uint32_t *table;
-    // (a prefix of one to three bytes leaves no history -- hist is a multiple of 4 -- but it is a prefix: the frames' windows were planned without
-    //  far history, as the twin does; found by reading, round 6: such a frame would have carried offsets beyond its window)
-    const uint64_t plen_eff = a.d_prefix ? a.prefix_len : 0, frame_max = frame_size < a.n ? frame_size : a.n;
-    if (!L.pl.hist && zke_ldm_in_frame(a.level, plen_eff, frame_max)) {
-        // in-frame far history (level >= 2, no prefix, frames beyond the ring's reach): one table per frame over its own bytes
-        ldm.inframe = 1; ldm.frame_size = frame_size; ldm.n_total = a.n; ldm.log = zke_ldm_log(frame_max);
+    if (p.kind == ZK_ENC_FAR_INFRAME) {
+        uint8_t *buf;
         if (a.list) {
-            // a table only for the frames that qualify, one behind the other after the shared empty one; their records go up in front of the tables
-            uint32_t nlf = 0;
-            for (uint32_t f = 0; f < nf; f++) nlf += zke_ldm_in_frame(a.level, plen_eff, zk_enc_frame_bytes(a, f));
-            const size_t lf_bytes = ((size_t)nlf * sizeof(ZkEncLdmFrame) + 63) & ~(size_t)63;
-            if ((rc = zk_pin_reserve(e, e->enc.pin_lf, e->enc.pin_lf_cap, lf_bytes))) return rc;
-            ZkEncLdmFrame *lf = (ZkEncLdmFrame *)e->enc.pin_lf;
-            uint64_t entries = zke_ldm_list_shared();
-            for (uint32_t f = 0, k = 0; f < nf; f++) if (zke_ldm_in_frame(a.level, plen_eff, zk_enc_frame_bytes(a, f))) {
-                lf[k++] = ZkEncLdmFrame{zk_enc_frame_src(a, f), entries, zk_enc_frame_bytes(a, f), 0};
-                entries += 1ull << zke_ldm_log(zk_enc_frame_bytes(a, f));
-            }
-            uint8_t *buf;
-            if ((rc = zk_enc_reserve(e, e->enc.ldm, lf_bytes + (size_t)entries * sizeof(uint32_t) + 64, &buf))) return rc;
-            ZK_HIP(hipMemcpyAsync(buf, lf, (size_t)nlf * sizeof(ZkEncLdmFrame), hipMemcpyHostToDevice, st));
-            table = (uint32_t *)(buf + lf_bytes);
-            ldm.lf = (const ZkEncLdmFrame *)buf; ldm.nlf = nlf;
-            if (zk_launch_enc_ldm_build_frames(st, L.src, ldm, table, nlf, entries, (uint32_t)frame_max)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
-        } else {
-            if ((rc = zk_enc_reserve(e, e->enc.ldm, (((size_t)nf * sizeof(uint32_t)) << ldm.log) + 64, &table))) return rc;
-            if (zk_launch_enc_ldm_build_frames(st, L.src, ldm, table, nf)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
+            // the records of the frames with a table go up in front of the tables
+            if ((rc = zk_pin_reserve(e, e->enc.pin_lf, e->enc.pin_lf_cap, p.lf_bytes))) return rc;
+            zk_enc_far_list_frames(L.cut, a.level, plen, (ZkEncLdmFrame *)e->enc.pin_lf);
         }
+        if ((rc = zk_enc_reserve(e, e->enc.ldm, p.lf_bytes + p.table_bytes + 64, &buf))) return rc;
+        if (a.list) {
+            ZK_HIP(hipMemcpyAsync(buf, e->enc.pin_lf, (size_t)ldm.nlf * sizeof(ZkEncLdmFrame), hipMemcpyHostToDevice, st));
+            ldm.lf = (const ZkEncLdmFrame *)buf;
+        }
+        table = (uint32_t *)(buf + p.lf_bytes);
+        if (zk_launch_enc_ldm_build_frames(st, L.src, ldm, table, a.list ? ldm.nlf : L.pl.nf, p.table_bytes, p.build_gx)) { e->last_err = "hipMemsetAsync (in-frame long-distance table)"; return ZK_ERR_HIP; }
         ldm.table = table;
-        if (zke_dense_in_frame(a.level, plen_eff, frame_max)) {
-            // dense far history (level 0 / >= 3): a far candidate per input byte, 4 bytes each (with the sorted positions 8 x the input: HBM is what this device has)
-            ldm.dlog = zke_dense_log(a.level);
-            // + as much again for the positions sorted by the pass their slot belongs to, and a word per segment and pass (+ 1)
-            // -- for a SLICE of whole frames at a time (at most dense_slice bytes of input: 4 GiB unless ZK_CHOICE_ENC_DENSE_SLICE_KIB says
-            // otherwise, which the tests use): the dense kernels and the match kernel run slice after slice over the same scratch, so a call
-            // of any size takes at most 8 x 4 GiB of it
-            const uint64_t dense_slice = e->enc.dense_slice_bytes ? e->enc.dense_slice_bytes : 4ull << 30;
-            L.slice_cap = dense_slice > frame_size ? dense_slice : frame_size;
-            L.dense_span = (size_t)(a.n < L.slice_cap ? a.n : L.slice_cap);
-            if (L.slice_cap >= a.n) L.slice_cap = 0;
-            if ((rc = zk_enc_reserve(e, e->enc.dense, (2 * (L.dense_span + ZKE_DENSE_SLACK) + (size_t)L.pl.nseg * (ZKE_DENSE_PASSES_MAX + 1)) * sizeof(uint32_t) + 64, &L.cand))) return rc;
-            L.part = L.cand + (L.dense_span + ZKE_DENSE_SLACK); L.poff = L.part + (L.dense_span + ZKE_DENSE_SLACK);
+        if (p.dense_span) {
+            L.slice_cap = p.slice_cap;
+            if ((rc = zk_enc_reserve(e, e->enc.dense, (2 * p.cand_words + p.poff_words) * sizeof(uint32_t) + 64, &L.cand))) return rc;
+            L.part = L.cand + p.cand_words; L.poff = L.part + p.cand_words;
             ldm.dense = L.cand;
         }
     }
-    if (L.pl.hist && a.prefix_len > ZKE_WINDOW) {
-        const uint64_t usable = zke_ldm_usable(a.prefix_len);
-        ldm.pfx = (const uint8_t *)a.d_prefix; ldm.plen = a.prefix_len; ldm.u0 = a.prefix_len - usable; ldm.log = zke_ldm_log(usable);
-        if ((rc = zk_enc_reserve(e, e->enc.ldm, (sizeof(uint32_t) << ldm.log) + 64, &table))) return rc;
-        if (zk_launch_enc_ldm_build(st, ldm, table)) { e->last_err = "hipMemsetAsync (long-distance table)"; return ZK_ERR_HIP; }
+    if (p.kind == ZK_ENC_FAR_PREFIX) {
+        ldm.pfx = (const uint8_t *)a.d_prefix;
+        if ((rc = zk_enc_reserve(e, e->enc.ldm, p.table_bytes + 64, &table))) return rc;
+        if (zk_launch_enc_ldm_build(st, ldm, table, p.table_bytes, p.build_gx)) { e->last_err = "hipMemsetAsync (long-distance table)"; return ZK_ERR_HIP; }
         ldm.table = table;
     }
     return 0;
 }
 
-// the match pass, slice after slice of whole frames: the dense candidates of a slice, then the matcher over its segments.  Without
-// dense history, or when its scratch spans the whole input, everything is one slice.  The candidate arrays are indexed like the
-// source, so a slice's kernels get them shifted by the slice's first byte.  Timed: the two kernels of one slice each by itself;
+// the match pass, slice after slice of whole frames (zk_enc_slice_end): the dense candidates of a slice, then the matcher over its
+// segments.  Without dense history, or when its scratch spans the whole input, everything is one slice.  The candidate arrays are indexed
+// like the source, so a slice's kernels get them shifted by the slice's first byte.  Timed: the two kernels of one slice each by itself;
 // of several, the whole loop as the match kernel.
 static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipStream_t st)
 {
-    const uint32_t nf = L.pl.nf, nseg = L.pl.nseg;
+    const uint32_t nf = L.pl.nf;
     const bool sliced = L.slice_cap != 0;   // (dense scratch or staged records below the call's size; never both: a prefix has no dense history)
     zk_kernel_timer whole(e, ZK_K_ENC_MATCH, st, sliced);
-    // where frame f's record ends in the matcher's source (without a prefix the frame's bytes in the input): what a slice is measured in
-    auto rec_end = [&](uint32_t f) { return f + 1 < nf ? zk_enc_frame_rec(a, L.pl.hist, f + 1) : L.rec_total; };
-    for (uint32_t f0 = 0, s0 = 0, f1, s1; f0 < nf; f0 = f1, s0 = s1) {
-        f1 = nf; s1 = nseg;
-        if (sliced) {
-            // whole frames while they fit, never less than one; a frame has a segment per ZKE_SEGMENT bytes
-            for (f1 = f0, s1 = s0; f1 < nf && (f1 == f0 || rec_end(f1) - zk_enc_frame_rec(a, L.pl.hist, f0) <= L.slice_cap); f1++) s1 += (zk_enc_frame_bytes(a, f1) + ZKE_SEGMENT - 1) / ZKE_SEGMENT;
-        }
-        const uint64_t lo = zk_enc_frame_src(a, f0);
+    for (uint32_t f0 = 0, s0 = 0; f0 < nf;) {
+        const ZkEncSlice end = zk_enc_slice_end(L.cut, L.pl.hist, L.rec_total, L.slice_cap, L.pl.nseg, f0, s0);
+        const uint32_t f1 = end.f1, s1 = end.s1;
+        const uint64_t lo = zk_enc_frame_src(L.cut, f0);
         ZkEncLdm sl = L.ldm;
         if (sl.dense) {
             sl.dense = L.cand - lo;
@@ -323,10 +265,11 @@ static int zk_enc_match(zk_engine *e, const zk_enc_args &a, ZkEncLayout &L, hipS
         if (L.stage) {
             // the slice's [content tail | frame] records: the frames' m_off count from the call's first record, so the buffer is handed on
             // shifted by the slice's first record (the next slice's staging runs behind this slice's matcher on the same queue)
-            L.msrc = L.stage - zk_enc_frame_rec(a, L.pl.hist, f0);
+            L.msrc = L.stage - zk_enc_frame_rec(L.cut, L.pl.hist, f0);
             zk_launch_enc_stage_hist(st, L.src, (const uint8_t *)a.d_prefix + (a.prefix_len - L.pl.hist), L.d_frames + f0, f1 - f0, (uint8_t *)L.msrc);
         }
         zk_launch_enc_match(st, L.msrc, L.d_segs + s0, s1 - s0, L.d_blocks, L.seqs, L.lits, a.level, sl);
+        f0 = f1; s0 = s1;
     }
     return 0;
 }

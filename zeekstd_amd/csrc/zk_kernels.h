@@ -58,10 +58,10 @@ void zk_launch_enc_plan_fill(hipStream_t st, const uint64_t *d_off, uint32_t cou
                              ZkEncFrame *frames, ZkEncBlock *blocks, ZkEncFrame *segs, uint64_t *doff);
 void zk_launch_enc_stage_hist(hipStream_t st, const uint8_t *src, const uint8_t *prefix_tail, const ZkEncFrame *frames, uint32_t nframes, uint8_t *stage);
 void zk_launch_enc_match(hipStream_t st, const uint8_t *src, const ZkEncFrame *segs, uint32_t nsegs, ZkEncBlock *blocks, uint64_t *seqs, uint8_t *lits, int level, const ZkEncLdm &ldm);
-int zk_launch_enc_ldm_build(hipStream_t st, const ZkEncLdm &ldm, uint32_t *table);                        // 0, or -1: the table could not be cleared
+int zk_launch_enc_ldm_build(hipStream_t st, const ZkEncLdm &ldm, uint32_t *table, size_t table_bytes, uint32_t gx);     // 0, or -1: the table could not be cleared (sizes: ZkEncFarPlan)
 // cand, part: an entry per input byte + ZKE_DENSE_SLACK; poff: (ZKE_DENSE_PASSES_MAX + 1) words per segment; every entry that is read is written first: no clear
 void zk_launch_enc_dense_cand(hipStream_t st, const uint8_t *src, const ZkEncFrame *segs, uint32_t nsegs, const ZkEncLdm &ldm, uint32_t *cand, uint32_t *part, uint32_t *poff);
-int zk_launch_enc_ldm_build_frames(hipStream_t st, const uint8_t *src, const ZkEncLdm &ldm, uint32_t *table, uint32_t nframes, uint64_t list_entries = 0, uint32_t list_max = 0);
+int zk_launch_enc_ldm_build_frames(hipStream_t st, const uint8_t *src, const ZkEncLdm &ldm, uint32_t *table, uint32_t nframes, size_t table_bytes, uint32_t gx);
 void zk_launch_enc_fse_build(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, uint32_t nframes, const ZkEncBlock *blocks, uint64_t *seqs, uint32_t *mpos,
                              const ZkEncTables *predef, ZkEncTables *ftab, const ZkEncDictDev *dd = nullptr);
 void zk_launch_enc_entropy(hipStream_t st, const uint8_t *src, const ZkEncFrame *frames, ZkEncBlock *blocks, uint32_t nblocks,
