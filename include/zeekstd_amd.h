@@ -121,9 +121,15 @@ enum {
     ZK_CHOICE_TRAIN_TRIAL_KIB = 18,    /* zk_train_dictionary*: KiB of samples above which the candidates are tried, and the tables measured, on every j-th
                                         * sample (1..2^22; 0 = 2^16, 64 MiB).  Unlike the keys above it is part of the function: it decides which samples
                                         * the choice of k and the tables see.  The tests reach the rule with small inputs through it */
-    ZK_CHOICE_CDC_SLICE_KIB = 19       /* zk_chunk_boundaries*: input KiB whose candidates the engine holds at a time (1..2^22; 0 = 2^16, 64 MiB).  A longer
+    ZK_CHOICE_CDC_SLICE_KIB = 19,      /* zk_chunk_boundaries*: input KiB whose candidates the engine holds at a time (1..2^22; 0 = 2^16, 64 MiB).  A longer
                                         * input is marked and selected slice after slice, the chain's cut carried across.  The offsets do not depend on it;
                                         * the scratch (up to 4 1/4 bytes per byte of a slice) does */
+    ZK_CHOICE_DEDUP_KEY_BITS = 20,     /* zk_dedup_frames* / zk_encode_dedup*: only the low k bits of a frame's key (a 64-bit hash and the length) group the frames that
+                                        * are then compared byte for byte (1..64; 0 = all 64).  The outputs do not depend on it: with 1-4 bits nearly every
+                                        * frame meets a wrong leader and the rounds that settle one content per key run many times, which no real input
+                                        * provokes.  Like ZK_CHOICE_TRAIN_TRIAL_KIB it lets small inputs reach the rule's rare path */
+    ZK_CHOICE_DEDUP_SLICE_KIB = 21     /* zk_encode_dedup*: KiB of unique frames gathered into engine scratch and encoded at a time, whole frames, one at
+                                        * least (1..2^22; 0 = 2^20, 1 GiB).  The bytes do not depend on it; the scratch does */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -316,6 +322,7 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *   zk_encode_frame_list[_dev]                                                      served    served    served     (the encoder's scratch, as the rows above)
  *   zk_train_dictionary[_dev]                                                       served    served    served     (the encoder's scratch and its frame-list route)
  *   zk_chunk_boundaries[_dev], zk_encode_chunked[_dev]                              served    served    served     (the encoder's scratch and its frame-list route)
+ *   zk_dedup_frames[_dev], zk_encode_dedup[_dev]                                    served    served    served     (the encoder's scratch and its frame-list route)
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
  *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
@@ -544,6 +551,52 @@ int zk_encode_chunked_dev(zk_engine *e, const void *d_src, uint64_t n, const zk_
 int zk_encode_chunked(zk_engine *e, const uint8_t *src, uint64_t n, const zk_chunk_params *p, int level, int checksum,
                       const uint8_t *prefix, uint64_t prefix_len, const zk_cdict *cdict, uint8_t *dst, uint64_t dst_cap,
                       uint64_t *off_out, uint32_t off_cap, uint32_t *c_sizes, uint32_t *d_sizes, uint32_t *n_frames, uint64_t *written);
+
+/* ---- Duplicate frames found on the device, and each distinct frame encoded once: what content-defined cuts are for (a VM image with repeated
+ * blocks, backups of several versions of a tree, logs with repeated records).  The reference has no counterpart.  off[count + 1] is the array
+ * zk_encode_frame_list[_dev] takes: non-decreasing, off[0] need not be 0, frame i is src[off[i], off[i + 1]).
+ * THE RULE, a pure function of the frames' bytes:
+ *   - ref[i] is the smallest j <= i whose frame has the same length and the same bytes as frame i.  ref[i] == i exactly for the first frame of
+ *     each distinct content; all empty frames are equal to each other
+ *   - uniq[0 .. n_unique) is the ascending list of the i with ref[i] == i
+ *   - ids[i] is the position of ref[i] in uniq: the array zk_decode_frame_list_dev takes as d_ids when the archive holds the uniq frames in
+ *     that order
+ * ref, ids (count entries) and uniq (n_unique entries; size it for count) are uint32, and each may be NULL; *n_unique is always set.
+ * The result is EXACT: it does not depend on the quality of any hash.  Frames are grouped by a 64-bit key (a hash of the bytes made for this purpose, and the length)
+ * and a frame is merged into a group's first frame only after all its bytes have been compared with that frame's; a frame that differs is
+ * grouped again among the frames still open, round after round, until every frame is settled.  ZK_CHOICE_DEDUP_KEY_BITS
+ * shortens the key so that tests reach those rounds; the outputs do not depend on it.
+ * ZK_ERR_ARGUMENT for a decreasing list or a frame above ZK_SEEKABLE_MAX_FRAME_SIZE; count > ZK_SEEKABLE_MAX_FRAMES is
+ * ZK_ERR_FRAME_INDEX_TOO_LARGE, decided before the list is read; count == 0 returns 0 with *n_unique = 0.  A refused call writes nothing to
+ * the arrays (*n_unique = 0).
+ * zk_dedup_frames_dev: d_src (any alignment, no padding needed: no load leaves [off[0], off[count])), d_off and the three arrays are device
+ * memory, n_unique is host memory.  The call SYNCHRONISES ITS STREAM: once at the start, when the offsets come to the host to be checked;
+ * once or twice per round (one round unless two different frames share a key) for the count of frames still open; and at the end.
+ * zk_dedup_frames (host pointers) uploads the source whole into engine scratch, off[count] - off[0] bytes; only the three arrays come back.
+ * zk_encode_dedup[_dev] is zk_dedup_frames[_dev] followed by zk_encode_frame_list[_dev] over the uniq frames only, on the plain, prefix or
+ * dictionary route: frame k of the output is byte for byte the frame that call makes of source frame uniq[k] alone, with the same level,
+ * checksum flag, prefix and cdict.  c_sizes / d_sizes (may be NULL) receive n_unique entries; size them for count.  *written is the sum of
+ * the c_sizes.  The unique frames are gathered back to back into engine scratch in slices of whole frames (ZK_CHOICE_DEDUP_SLICE_KIB) and
+ * encoded slice after slice into consecutive destinations; a list without duplicates is encoded where it lies.  The bytes do not depend on
+ * the slice.  dst_cap >= zk_compress_bound_list(n, count, with_dictionary), the bound of the list without any duplicate, always suffices;
+ * below it, -70 and "destination untouched" are as for zk_encode_frame_list_dev (with more than one slice the frames are then encoded
+ * twice, the first time into scratch).  The host-pointer call uploads the source whole and stages the prefix as zk_encode_frame_list does.
+ * READING BACK needs nothing new.  With c_off / d_off the prefix sums of the n_unique c_sizes / d_sizes,
+ *     zk_decode_frame_list_dev(e, d_comp, written, d_c_off, d_d_off, d_ids = ids, d_out_off = off - off[0], count, d_dst, off[count] - off[0], ...)
+ * reproduces src[off[0], off[count]): ids may repeat and come in any order.  Where ids is kept is the caller's business (a skippable frame
+ * is the obvious place); nothing is remembered from call to call. */
+int zk_dedup_frames_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count,
+                        void *d_ref, void *d_ids, void *d_uniq, uint32_t *n_unique, void *stream);
+int zk_dedup_frames(zk_engine *e, const uint8_t *src, const uint64_t *off, uint32_t count,
+                    uint32_t *ref, uint32_t *ids, uint32_t *uniq, uint32_t *n_unique);
+int zk_encode_dedup_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, int level, int checksum,
+                        const void *d_prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                        void *d_dst, uint64_t dst_cap, void *d_ids, void *d_uniq,
+                        void *d_c_sizes, void *d_d_sizes, uint32_t *n_unique, uint64_t *written, void *stream);
+int zk_encode_dedup(zk_engine *e, const uint8_t *src, const uint64_t *off, uint32_t count, int level, int checksum,
+                    const uint8_t *prefix, uint64_t prefix_len, const zk_cdict *cdict,
+                    uint8_t *dst, uint64_t dst_cap, uint32_t *ids, uint32_t *uniq,
+                    uint32_t *c_sizes, uint32_t *d_sizes, uint32_t *n_unique, uint64_t *written);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside

@@ -117,6 +117,12 @@ _sig = {
                                         _P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
     "zk_encode_chunked": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(ChunkParams), C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64,
                                     _P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "zk_dedup_frames_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32), _P]),
+    "zk_dedup_frames": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "zk_encode_dedup_dev": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, _P,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
+    "zk_encode_dedup": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, _P,
+                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

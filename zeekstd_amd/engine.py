@@ -124,7 +124,7 @@ class Engine:
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
                "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17, "train_trial_kib": 18,
-               "cdc_slice_kib": 19}
+               "cdc_slice_kib": 19, "dedup_key_bits": 20, "dedup_slice_kib": 21}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -385,6 +385,70 @@ class Engine:
         if rc != 0:
             self._raise(rc)
         return nfo.value, wr.value
+
+    def dedup_frames(self, data, offsets):
+        """zk_dedup_frames: which frames of `data` (cut by `offsets`, as encode_frame_list takes them) are byte-identical.  Returns
+        (ref, ids, uniq) as np.uint32 arrays: ref[i] the first frame with frame i's bytes, uniq the frames with ref[i] == i in ascending
+        order, ids[i] the position of ref[i] in uniq (what decode_frame_list_dev takes as d_ids for an archive of the uniq frames)."""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        off = _u64(offsets)
+        count = max(len(off) - 1, 0)
+        ref, ids, uniq = (np.zeros(max(count, 1), np.uint32) for _ in range(3))
+        nu = C.c_uint32()
+        rc = lib.zk_dedup_frames(self._h, data.ctypes.data if data.size else None, off.ctypes.data, count, ref.ctypes.data, ids.ctypes.data,
+                                 uniq.ctypes.data, C.byref(nu))
+        if rc != 0:
+            self._raise(rc)
+        return ref[:count], ids[:count], uniq[:nu.value]
+
+    def dedup_frames_dev(self, d_src, d_off, count, d_ref=None, d_ids=None, d_uniq=None, stream=None):
+        """zk_dedup_frames_dev: device tensors (or raw pointers) in and out; d_ref / d_ids / d_uniq: uint32 arrays of `count` entries, any
+        of them None.  Returns n_unique."""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        nu = C.c_uint32()
+        rc = lib.zk_dedup_frames_dev(self._h, opt(d_src), opt(d_off), count, opt(d_ref), opt(d_ids), opt(d_uniq), C.byref(nu), stream)
+        if rc != 0:
+            self._raise(rc)
+        return nu.value
+
+    def encode_dedup_dev(self, d_src, d_off, count, level, checksum, d_dst, dst_cap, d_ids=None, d_uniq=None, d_c_sizes=None, d_d_sizes=None,
+                         d_prefix=None, prefix_len=0, dictionary=None, stream=None):
+        """zk_encode_dedup_dev: every distinct frame of the list encoded once, device tensors in and out (d_ids / d_uniq / d_c_sizes /
+        d_d_sizes: uint32, `count` entries each).  Returns (n_unique, bytes written)."""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        nu = C.c_uint32()
+        wr = C.c_uint64()
+        rc = lib.zk_encode_dedup_dev(self._h, opt(d_src), opt(d_off), count, level, int(checksum), opt(d_prefix), prefix_len,
+                                     dictionary._h if dictionary is not None else None, opt(d_dst), dst_cap, opt(d_ids), opt(d_uniq),
+                                     opt(d_c_sizes), opt(d_d_sizes), C.byref(nu), C.byref(wr), stream)
+        if rc != 0:
+            self._raise(rc)
+        return nu.value, wr.value
+
+    def encode_dedup(self, data, offsets=None, avg_size=0, min_size=0, max_size=0, level=1, checksum=False, prefix=None, dictionary=None):
+        """zk_encode_dedup: one zstd frame per DISTINCT frame of `data`.  offsets: the frames (as encode_frame_list takes them); None: the
+        content-defined boundaries of chunk_boundaries(data, avg_size, min_size, max_size) first.  Returns (compressed payload bytes of the
+        unique frames, np.uint64 offsets of all frames, np.uint32 c_sizes and d_sizes of the unique frames, np.uint32 ids: frame i of the
+        input is archive frame ids[i]).  prefix / dictionary as encode_frames."""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        if dictionary is not None and prefix:
+            raise ValueError("a prefix and a dictionary exclude each other at this level")
+        off = self.chunk_boundaries(data, avg_size, min_size, max_size) if offsets is None else _u64(offsets)
+        count = max(len(off) - 1, 0)
+        n = int(off[count] - off[0]) if count and off[count] >= off[0] else 0
+        cap = int(lib.zk_compress_bound_list(n, count, int(dictionary is not None)))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        cs, ds, ids, uniq = (np.zeros(max(count, 1), np.uint32) for _ in range(4))
+        nu = C.c_uint32()
+        wr = C.c_uint64()
+        pre = np.frombuffer(bytes(prefix), dtype=np.uint8) if prefix else None
+        rc = lib.zk_encode_dedup(self._h, data.ctypes.data if data.size else None, off.ctypes.data, count, level, int(checksum),
+                                 pre.ctypes.data if pre is not None else None, pre.size if pre is not None else 0,
+                                 dictionary._h if dictionary is not None else None, out.ctypes.data, cap, ids.ctypes.data, uniq.ctypes.data,
+                                 cs.ctypes.data, ds.ctypes.data, C.byref(nu), C.byref(wr))
+        if rc != 0:
+            self._raise(rc)
+        return out[:wr.value].tobytes(), off, cs[:nu.value].copy(), ds[:nu.value].copy(), ids[:count].copy()
 
     @staticmethod
     def _train_params(k, d, f, level, dict_id, raw_content):
