@@ -128,8 +128,11 @@ enum {
                                         * are then compared byte for byte (1..64; 0 = all 64).  The outputs do not depend on it: with 1-4 bits nearly every
                                         * frame meets a wrong leader and the rounds that settle one content per key run many times, which no real input
                                         * provokes.  Like ZK_CHOICE_TRAIN_TRIAL_KIB it lets small inputs reach the rule's rare path */
-    ZK_CHOICE_DEDUP_SLICE_KIB = 21     /* zk_encode_dedup*: KiB of unique frames gathered into engine scratch and encoded at a time, whole frames, one at
+    ZK_CHOICE_DEDUP_SLICE_KIB = 21,    /* zk_encode_dedup*: KiB of unique frames gathered into engine scratch and encoded at a time, whole frames, one at
                                         * least (1..2^22; 0 = 2^20, 1 GiB).  The bytes do not depend on it; the scratch does */
+    ZK_CHOICE_DEDUP_PASS_KIB = 22      /* zk_dedup_against_dev / zk_encode_dedup_against_dev / zk_dedup_index_add_archive_dev: KiB of archive frames decoded
+                                        * into engine scratch at a time, whole frames, one at least (1..2^22; 0 = 2^20, 1 GiB).  The results do not
+                                        * depend on it; the scratch does */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -323,6 +326,10 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *   zk_train_dictionary[_dev]                                                       served    served    served     (the encoder's scratch and its frame-list route)
  *   zk_chunk_boundaries[_dev], zk_encode_chunked[_dev]                              served    served    served     (the encoder's scratch and its frame-list route)
  *   zk_dedup_frames[_dev], zk_encode_dedup[_dev]                                    served    served    served     (the encoder's scratch and its frame-list route)
+ *   zk_dedup_against_dev, zk_encode_dedup_against_dev,                              refused   served    refused    (the candidates are decoded on context 0;
+ *     zk_dedup_index_add_archive_dev                                                                                *n_fresh, the arrays and the index stay)
+ *   zk_dedup_index_create / _free / _count / _add[_dev] / _export / _truncate,      served    served    served     (memory of the index's own, the encoder's scratch)
+ *     zk_frame_keys[_dev]
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
  *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
@@ -584,7 +591,7 @@ int zk_encode_chunked(zk_engine *e, const uint8_t *src, uint64_t n, const zk_chu
  * READING BACK needs nothing new.  With c_off / d_off the prefix sums of the n_unique c_sizes / d_sizes,
  *     zk_decode_frame_list_dev(e, d_comp, written, d_c_off, d_d_off, d_ids = ids, d_out_off = off - off[0], count, d_dst, off[count] - off[0], ...)
  * reproduces src[off[0], off[count]): ids may repeat and come in any order.  Where ids is kept is the caller's business (a skippable frame
- * is the obvious place); nothing is remembered from call to call. */
+ * is the obvious place); nothing is remembered from call to call -- that is what zk_dedup_index and zk_encode_dedup_against_dev, below, are for. */
 int zk_dedup_frames_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count,
                         void *d_ref, void *d_ids, void *d_uniq, uint32_t *n_unique, void *stream);
 int zk_dedup_frames(zk_engine *e, const uint8_t *src, const uint64_t *off, uint32_t count,
@@ -597,6 +604,82 @@ int zk_encode_dedup(zk_engine *e, const uint8_t *src, const uint64_t *off, uint3
                     const uint8_t *prefix, uint64_t prefix_len, const zk_cdict *cdict,
                     uint8_t *dst, uint64_t dst_cap, uint32_t *ids, uint32_t *uniq,
                     uint32_t *c_sizes, uint32_t *d_sizes, uint32_t *n_unique, uint64_t *written);
+
+/* ---- A frame list deduplicated against an archive that already exists: tonight's backup against last night's, version N + 1 of an image
+ * against version N, a chunk store that grows.  The reference has no counterpart.  An ARCHIVE is what zk_decode_frame_list_dev reads: d_comp,
+ * d_c_off, d_d_off, n_frames, all in device memory.  A zk_dedup_index knows its first m frames (m = zk_dedup_index_count).
+ * THE RULE, a pure function of the decoded archive frames 0 .. m-1 and the list's bytes (off[count + 1] as everywhere else):
+ *   - ids[i] is the smallest archive frame s < m whose decoded bytes and length equal frame i's, where one exists
+ *   - otherwise let j be the smallest list index <= i with frame i's bytes: j is FRESH, and ids[i] = m + (the position of j in fresh)
+ *   - fresh[0 .. n_fresh) is the ascending list of such j
+ *   - all empty frames are equal, to each other and to an empty archive frame
+ *   - with m == 0, ids and fresh are exactly ids and uniq of zk_dedup_frames
+ *   - after the fresh frames are appended to the archive in that order, zk_decode_frame_list_dev over the grown archive with d_ids = ids and
+ *     d_out_off = off - off[0] reproduces src[off[0], off[count])
+ * ids (count entries) and fresh (n_fresh entries; size it for count) are uint32 and may be NULL; *n_fresh is always set.
+ * The result is EXACT: a frame is mapped to an archive frame only after every one of its bytes has been compared with that frame's DECODED
+ * bytes.  The key decides the time, never the result.
+ * THE FRAME KEY, a stored format from here on (an exported index holds it): the frame is read as little-endian 8-byte words counted from its
+ * own first byte, zero-padded to a multiple of 16 bytes; word w of value v gives the term
+ *     x = v + (w + 1) * 0x9E3779B97F4A7C15;  x ^= x >> 33;  x *= 0xFF51AFD7ED558CCD;  x ^= x >> 33;  x *= 0xC4CEB9FE1A85EC53;  x ^= x >> 33
+ * (all mod 2^64), and the key is (the sum of the terms' low 32 bits mod 2^32) | (the sum of their high 32 bits mod 2^32) << 32.  The empty
+ * frame's key is 0.  The length is not part of it: the index keeps it beside the key.  zk_frame_keys[_dev] writes count keys (uint64; the
+ * device array 8-byte aligned); list errors as for zk_dedup_frames.
+ * THE INDEX lives on the device: the full 64-bit keys and the lengths of its m frames, and an open-addressing table of 32-bit archive ids that
+ * persists between calls.  Every frame has a slot of its own (equal keys are not merged: the archive may hold duplicates), taken by
+ * compare-and-swap, linear probing from the home of its key cut to ZK_CHOICE_DEDUP_KEY_BITS as in force when the index was created.  The table
+ * keeps at least twice as many slots as frames and is rebuilt at twice the size from the keys when an add would cross that.
+ *   zk_dedup_index_create       an empty index (NULL when the device gives no memory); zk_dedup_index_free(NULL) is allowed
+ *   zk_dedup_index_add[_dev]    frames m .. m + count - 1 from their keys (uint64) and decoded sizes (uint32).  An index made by add from
+ *                               exported arrays behaves exactly like the one they were exported from
+ *   zk_dedup_index_add_archive_dev   decodes archive frames m .. n_frames - 1 (checksums verified, against the engine's dictionary if one is
+ *                               set) in passes of ZK_CHOICE_DEDUP_PASS_KIB, keys them and adds them; a frame that fails returns its -(code) and
+ *                               leaves the index as it was.  n_frames < m is ZK_ERR_ARGUMENT
+ *   zk_dedup_index_export       keys and sizes of frames [first, first + count) to host arrays (either may be NULL)
+ *   zk_dedup_index_truncate     forgets frames >= count (an append the caller could not keep); the table is rebuilt
+ * m + count above ZK_SEEKABLE_MAX_FRAMES is ZK_ERR_FRAME_INDEX_TOO_LARGE.  Every call that changes the index synchronises its stream.  An index
+ * belongs to the engine it was made on and must be freed before it.
+ * zk_dedup_against_dev: the in-call map of zk_dedup_frames_dev first; then, in rounds, every unique frame still open looks up the smallest
+ * index entry of its key and length above the one it tried last; the round's candidates are decoded on context 0 -- the route of
+ * zk_decode_frame_list_dev, checksums verified, against the engine's dictionary if one is set -- into engine scratch in passes of at most
+ * ZK_CHOICE_DEDUP_PASS_KIB (one whole frame at least), and each is compared with its source frame byte for byte.  Equal settles the frame on
+ * that archive frame; different opens it again.  Candidates ascend, so the first match is the smallest s.  One round unless an
+ * archive frame shares key and length with a different frame.  The call SYNCHRONISES ITS STREAM as zk_dedup_frames_dev does, and then once per
+ * round for the candidates, once per pass, once per round for the verdicts, and at the end.
+ *   - n_frames < m is ZK_ERR_ARGUMENT; frames at or beyond m are not looked at.  An index entry whose length is not the archive's is never a match
+ *   - a candidate that fails to decode or verify returns its -(code): the arrays are not written, *n_fresh = 0, the index is unchanged
+ *   - list errors, count == 0 and NULL outputs as for zk_dedup_frames_dev; a refused call writes nothing to the arrays (*n_fresh = 0)
+ * zk_encode_dedup_against_dev runs that map and then encodes the fresh frames exactly as zk_encode_dedup_dev encodes its uniq frames (gathered
+ * in slices of ZK_CHOICE_DEDUP_SLICE_KIB, through zk_encode_frame_list_dev, the same bound, -70 with the destination and the arrays
+ * untouched): output frame k is byte for byte what the list call makes of source frame fresh[k] alone.  c_sizes / d_sizes (may be NULL) receive
+ * n_fresh entries; size them for count.  On success, and only then, the fresh frames' keys and lengths are added to the index -- they are known
+ * from the map, nothing is decoded -- so that m grows by n_fresh.  The caller appends the payload to the archive and extends c_off / d_off
+ * from c_sizes / d_sizes (or calls zk_dedup_index_truncate when it cannot).  There is no prefix route: the verifying decode takes no prefix, so
+ * the call has no prefix parameters.  cdict is allowed; the verification of later calls then needs the matching dictionary set on the engine
+ * (zk_engine_set_dictionary), which is the caller's business.
+ * Not here: Level-B handles, host-pointer forms of the two `against` calls, an on-disk container for ids or for an exported index, removing
+ * frames from an archive. */
+typedef struct zk_dedup_index zk_dedup_index;
+zk_dedup_index *zk_dedup_index_create(zk_engine *e);
+void zk_dedup_index_free(zk_dedup_index *x);
+uint32_t zk_dedup_index_count(const zk_dedup_index *x);
+int zk_dedup_index_add(zk_dedup_index *x, const uint64_t *keys, const uint32_t *d_sizes, uint32_t count);
+int zk_dedup_index_add_dev(zk_dedup_index *x, const void *d_keys, const void *d_d_sizes, uint32_t count, void *stream);
+int zk_dedup_index_add_archive_dev(zk_dedup_index *x, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off,
+                                   uint32_t n_frames, void *stream);
+int zk_dedup_index_export(const zk_dedup_index *x, uint32_t first, uint32_t count, uint64_t *keys_out, uint32_t *d_sizes_out);
+int zk_dedup_index_truncate(zk_dedup_index *x, uint32_t count);
+int zk_frame_keys_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count, void *d_keys, void *stream);
+int zk_frame_keys(zk_engine *e, const uint8_t *src, const uint64_t *off, uint32_t count, uint64_t *keys);
+int zk_dedup_against_dev(zk_engine *e, const zk_dedup_index *x,
+                         const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off, uint32_t n_frames,
+                         const void *d_src, const void *d_off, uint32_t count,
+                         void *d_ids, void *d_fresh, uint32_t *n_fresh, void *stream);
+int zk_encode_dedup_against_dev(zk_engine *e, zk_dedup_index *x,
+                                const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off, uint32_t n_frames,
+                                const void *d_src, const void *d_off, uint32_t count, int level, int checksum, const zk_cdict *cdict,
+                                void *d_dst, uint64_t dst_cap, void *d_ids, void *d_fresh, void *d_c_sizes, void *d_d_sizes,
+                                uint32_t *n_fresh, uint64_t *written, void *stream);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside

@@ -4,7 +4,7 @@ Python mirror of the C ABI in include/zeekstd_amd.h.  Requires the in-tree HIP l
 there is no CPU fallback (import fails loudly without libzeekstd_amd.so).
 """
 from ._lib import LIB_PATH, TRAIN_RAW_CONTENT, TrainParams, TrainReport, error_name, lib  # noqa: F401
-from .engine import Dictionary, EncodeDictionary, Engine, ZkError  # noqa: F401
+from .engine import DedupIndex, DedupStore, Dictionary, EncodeDictionary, Engine, ZkError  # noqa: F401
 from .api import (CompressionProgress, DecodeOptions, Decoder, EncodeOptions, Encoder, EpilogueProgress, Error, Format,  # noqa: F401,E402
                   FrameSizePolicy, RawEncoder, SeekFrom, SeekTable, Serializer)
 

@@ -123,6 +123,19 @@ _sig = {
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
     "zk_encode_dedup": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, _P,
                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "zk_dedup_index_create": (_P, [_P]),
+    "zk_dedup_index_free": (None, [_P]),
+    "zk_dedup_index_count": (C.c_uint32, [_P]),
+    "zk_dedup_index_add": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "zk_dedup_index_add_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "zk_dedup_index_add_archive_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P]),
+    "zk_dedup_index_export": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "zk_dedup_index_truncate": (C.c_int, [_P, C.c_uint32]),
+    "zk_frame_keys_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
+    "zk_frame_keys": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "zk_dedup_against_dev": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), _P]),
+    "zk_encode_dedup_against_dev": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, _P, C.c_uint64,
+                                              _P, _P, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

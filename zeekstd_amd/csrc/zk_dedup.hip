@@ -352,3 +352,7 @@ extern "C" int zk_encode_dedup(zk_engine *e, const uint8_t *src, const uint64_t 
     if (written) *written = wr;
     return 0;
 }
+
+// zk_dedup_against_dev and its siblings build on the map and the encode above and on the kernels of zk_dedup.h, which one translation unit
+// only can define: they are compiled here
+#include "zk_dedup_index.hip"

@@ -11,7 +11,8 @@ enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_
        ZK_K_ENC_MATCH, ZK_K_ENC_ENTROPY, ZK_K_ENC_COMPACT, ZK_K_ENC_XXH64, ZK_K_ENC_FSE_BUILD, ZK_K_ENC_DENSE,
        ZK_K_RANGE_PLAN, ZK_K_RANGE_PIECES, ZK_K_RANGE_GATHER, ZK_K_RANGE_STATUS,
        ZK_K_TRAIN_COUNT, ZK_K_TRAIN_SELECT, ZK_K_TRAIN_STATS, ZK_K_CDC_MARK, ZK_K_CDC_SELECT,
-       ZK_K_DEDUP_HASH, ZK_K_DEDUP_INSERT, ZK_K_DEDUP_VERIFY, ZK_K_DEDUP_VERIFY_LONG, ZK_K_DEDUP_COMPACT, ZK_K_DEDUP_GATHER, ZK_NKERNELS };
+       ZK_K_DEDUP_HASH, ZK_K_DEDUP_INSERT, ZK_K_DEDUP_VERIFY, ZK_K_DEDUP_VERIFY_LONG, ZK_K_DEDUP_COMPACT, ZK_K_DEDUP_GATHER,
+       ZK_K_DXI_INSERT, ZK_K_DXI_LOOKUP, ZK_K_DXI_COMPARE, ZK_K_DXI_EMIT, ZK_NKERNELS };
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };
@@ -90,9 +91,11 @@ struct zk_engine {
         zk_devbuf cdc, cdc_src, cdc_off;    // zk_chunk_boundaries*: a slice's scratch (zk_cdc.hip); the host entry point's upload of a slice, and its offsets
         zk_devbuf dd, dd_src, dd_off, dd_dry, dd_up, dd_out;    // zk_dedup_frames* / zk_encode_dedup* (zk_dedup.hip): the map's scratch (ZkDedupLayout); a gathered slice of unique frames and its offsets; a slice encoded for its size only; the host entry points' upload of source and offsets, and their outputs
         uint8_t *pin_dd = nullptr; size_t pin_dd_cap = 0;     // ... the caller's offsets and the unique frames' indices, brought to the host
+        zk_devbuf dx;                       // zk_dedup_against_dev / zk_encode_dedup_against_dev (zk_dedup_index.hip): the lookup's scratch (ZkDxLayout); the decoded candidates of a pass lie in dctx[0].rng
         int plan_choice = 0;                // ZK_CHOICE_ENC_PLAN
         uint32_t dedup_key_bits = 0;        // zk_dedup_frames*: bits of a frame's key that are kept (0 = all 64), ZK_CHOICE_DEDUP_KEY_BITS
         uint64_t dedup_slice_bytes = 0;     // zk_encode_dedup*: bytes of unique frames gathered and encoded at a time (0 = 1 GiB), ZK_CHOICE_DEDUP_SLICE_KIB
+        uint64_t dedup_pass_bytes = 0;      // zk_dedup_against_dev, zk_dedup_index_add_archive_dev: decoded bytes of archive frames held at a time (0 = 1 GiB), ZK_CHOICE_DEDUP_PASS_KIB
         uint64_t cdc_slice_bytes = 0;       // zk_chunk_boundaries*: input bytes whose candidates are held at a time (0 = 64 MiB), ZK_CHOICE_CDC_SLICE_KIB
         uint64_t train_trial_bytes = 0;     // zk_train_dictionary*: sample bytes the candidates are tried on (0 = 64 MiB), ZK_CHOICE_TRAIN_TRIAL_KIB
         uint64_t dense_slice_bytes = 0;     // input bytes the dense scratch is reserved for (0 = 4 GiB), ZK_CHOICE_ENC_DENSE_SLICE_KIB

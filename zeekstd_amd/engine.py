@@ -124,7 +124,7 @@ class Engine:
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
                "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17, "train_trial_kib": 18,
-               "cdc_slice_kib": 19, "dedup_key_bits": 20, "dedup_slice_kib": 21}
+               "cdc_slice_kib": 19, "dedup_key_bits": 20, "dedup_slice_kib": 21, "dedup_pass_kib": 22}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -450,6 +450,49 @@ class Engine:
             self._raise(rc)
         return out[:wr.value].tobytes(), off, cs[:nu.value].copy(), ds[:nu.value].copy(), ids[:count].copy()
 
+    def frame_keys(self, data, offsets):
+        """zk_frame_keys: the 64-bit key of every frame of `data` (cut by `offsets`) as a dedup index stores it -> np.uint64 array"""
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        off = _u64(offsets)
+        count = max(len(off) - 1, 0)
+        keys = np.zeros(max(count, 1), np.uint64)
+        rc = lib.zk_frame_keys(self._h, data.ctypes.data if data.size else None, off.ctypes.data, count, keys.ctypes.data)
+        if rc != 0:
+            self._raise(rc)
+        return keys[:count]
+
+    def frame_keys_dev(self, d_src, d_off, count, d_keys, stream=None):
+        """zk_frame_keys_dev: device tensors (or raw pointers); d_keys: count uint64 words, 8-byte aligned"""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        rc = lib.zk_frame_keys_dev(self._h, opt(d_src), opt(d_off), count, opt(d_keys), stream)
+        if rc != 0:
+            self._raise(rc)
+
+    def dedup_against_dev(self, index, d_comp, comp_size, d_c_off, d_d_off, n_frames, d_src, d_off, count, d_ids=None, d_fresh=None, stream=None):
+        """zk_dedup_against_dev: which frames of the list the archive (d_comp, d_c_off, d_d_off, n_frames; known to `index`) already holds.
+        d_ids / d_fresh: uint32 device arrays of `count` entries, or None.  Returns n_fresh."""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        nf = C.c_uint32()
+        rc = lib.zk_dedup_against_dev(self._h, index._h, opt(d_comp), comp_size, opt(d_c_off), opt(d_d_off), n_frames, opt(d_src), opt(d_off), count,
+                                      opt(d_ids), opt(d_fresh), C.byref(nf), stream)
+        if rc != 0:
+            self._raise(rc)
+        return nf.value
+
+    def encode_dedup_against_dev(self, index, d_comp, comp_size, d_c_off, d_d_off, n_frames, d_src, d_off, count, level, checksum, d_dst, dst_cap,
+                                 d_ids=None, d_fresh=None, d_c_sizes=None, d_d_sizes=None, dictionary=None, stream=None):
+        """zk_encode_dedup_against_dev: the frames of the list the archive does not hold yet, each encoded once; `index` learns them.
+        Returns (n_fresh, bytes written)."""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        nf = C.c_uint32()
+        wr = C.c_uint64()
+        rc = lib.zk_encode_dedup_against_dev(self._h, index._h, opt(d_comp), comp_size, opt(d_c_off), opt(d_d_off), n_frames, opt(d_src), opt(d_off), count,
+                                             level, int(checksum), dictionary._h if dictionary is not None else None, opt(d_dst), dst_cap, opt(d_ids),
+                                             opt(d_fresh), opt(d_c_sizes), opt(d_d_sizes), C.byref(nf), C.byref(wr), stream)
+        if rc != 0:
+            self._raise(rc)
+        return nf.value, wr.value
+
     @staticmethod
     def _train_params(k, d, f, level, dict_id, raw_content):
         return _lib.TrainParams(k, d, f, level, dict_id, _lib.TRAIN_RAW_CONTENT if raw_content else 0)
@@ -594,3 +637,137 @@ class Engine:
         rc = lib.zk_xxh64_frames_dev(self._h, self._ptr(d_data), self._ptr(d_off), count, self._ptr(d_out), stream)
         if rc != 0:
             self._raise(rc)
+
+
+class DedupIndex:
+    """What an archive already holds, for Engine.dedup_against_dev / encode_dedup_against_dev (zk_dedup_index): the keys and lengths of its
+    frames and a table over them, on the device.  It keeps the engine alive; close() it before the engine."""
+
+    def __init__(self, engine):
+        h = lib.zk_dedup_index_create(engine._h)
+        if not h:
+            raise MemoryError("zk_dedup_index_create")
+        self._h = C.c_void_p(h)
+        self._engine = engine
+
+    @property
+    def count(self) -> int:
+        return int(lib.zk_dedup_index_count(self._h))
+
+    def __len__(self):
+        return self.count
+
+    def _check(self, rc):
+        if rc != 0:
+            self._engine._raise(rc)
+
+    def add(self, keys, d_sizes):
+        """the next len(keys) archive frames, from host arrays: their keys (Engine.frame_keys, or export) and decoded sizes"""
+        k = _u64(keys)
+        d = np.ascontiguousarray(np.asarray(d_sizes, dtype=np.uint32))
+        if len(k) != len(d):
+            raise ValueError("keys and d_sizes differ in length")
+        self._check(lib.zk_dedup_index_add(self._h, k.ctypes.data, d.ctypes.data, len(k)))
+
+    def add_dev(self, d_keys, d_d_sizes, count, stream=None):
+        self._check(lib.zk_dedup_index_add_dev(self._h, Engine._ptr(d_keys), Engine._ptr(d_d_sizes), count, stream))
+
+    def add_archive_dev(self, d_comp, comp_size, d_c_off, d_d_off, n_frames, stream=None):
+        """decodes the archive's frames count .. n_frames - 1 on the device, keys them and adds them"""
+        self._check(lib.zk_dedup_index_add_archive_dev(self._h, Engine._ptr(d_comp), comp_size, Engine._ptr(d_c_off), Engine._ptr(d_d_off), n_frames, stream))
+
+    def export(self, first=0, count=None):
+        """-> (keys np.uint64, d_sizes np.uint32) of frames [first, first + count)"""
+        count = self.count - first if count is None else count
+        keys, sizes = np.zeros(max(count, 1), np.uint64), np.zeros(max(count, 1), np.uint32)
+        self._check(lib.zk_dedup_index_export(self._h, first, count, keys.ctypes.data, sizes.ctypes.data))
+        return keys[:count], sizes[:count]
+
+    def truncate(self, count):
+        self._check(lib.zk_dedup_index_truncate(self._h, count))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._engine._h:
+                lib.zk_dedup_index_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DedupStore:
+    """A growing device-resident archive and its DedupIndex: append() stores the chunks the archive does not hold yet, read() returns any
+    list of chunks.  Python over the device calls only (chunk_boundaries_dev, encode_dedup_against_dev, decode_frame_list_dev)."""
+
+    def __init__(self, engine, level=1, checksum=True, dictionary=None):
+        import torch
+        self.engine, self.level, self.checksum, self.dictionary = engine, level, checksum, dictionary
+        self.index = DedupIndex(engine)
+        self._dev = torch.device("cuda", torch.cuda.current_device())
+        self._comp = torch.zeros(1 << 16, dtype=torch.uint8, device=self._dev)
+        self.comp_size = 0
+        self._c_off = np.zeros(1, np.uint64)
+        self._d_off = np.zeros(1, np.uint64)
+
+    @property
+    def n_frames(self) -> int:
+        return len(self._c_off) - 1
+
+    def _dev_u64(self, a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy()).to(self._dev)
+
+    def append(self, data, offsets=None, avg_size=0, min_size=0, max_size=0):
+        """Stores `data` cut by `offsets` (None: by content, chunk_boundaries_dev with avg_size / min_size / max_size).  Returns (ids, offsets):
+        np.uint32 archive frame of every chunk, np.uint64 offsets of the chunks; read(ids, offsets) returns the data."""
+        import torch
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        n = len(data)
+        d_src = torch.from_numpy(data.copy()).to(self._dev) if n else torch.zeros(1, dtype=torch.uint8, device=self._dev)
+        d_off = self.engine.chunk_boundaries_dev(d_src, n, avg_size, min_size, max_size) if offsets is None else self._dev_u64(offsets)
+        off = d_off.cpu().numpy().view(np.uint64).copy()
+        count = len(off) - 1
+        if count <= 0:
+            return np.zeros(0, np.uint32), off
+        nb = int(off[count] - off[0])
+        bound = int(lib.zk_compress_bound_list(nb, count, int(self.dictionary is not None)))
+        need = self.comp_size + bound + 64
+        if need > self._comp.numel():
+            grown = torch.zeros(max(need, 2 * self._comp.numel()), dtype=torch.uint8, device=self._dev)
+            grown[:self.comp_size] = self._comp[:self.comp_size]
+            self._comp = grown
+        ids, fresh, cs, ds = (torch.zeros(count, dtype=torch.int32, device=self._dev) for _ in range(4))
+        m = self.n_frames
+        torch.cuda.synchronize()
+        nf, wr = self.engine.encode_dedup_against_dev(self.index, self._comp, self.comp_size, self._dev_u64(self._c_off), self._dev_u64(self._d_off), m,
+                                                      d_src, d_off, count, self.level, self.checksum, self._comp.data_ptr() + self.comp_size, bound, ids,
+                                                      fresh, cs, ds, dictionary=self.dictionary)
+        self._c_off = np.concatenate([self._c_off, self._c_off[-1] + np.cumsum(cs[:nf].cpu().numpy().view(np.uint32), dtype=np.uint64)])
+        self._d_off = np.concatenate([self._d_off, self._d_off[-1] + np.cumsum(ds[:nf].cpu().numpy().view(np.uint32), dtype=np.uint64)])
+        self.comp_size += wr
+        return ids.cpu().numpy().view(np.uint32).copy(), off
+
+    def read(self, ids, offsets):
+        """the bytes of archive frames `ids` laid out by `offsets` (both as append returned them)"""
+        import torch
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32))
+        off = _u64(offsets)
+        count = len(ids)
+        if count == 0:
+            return b""
+        n = int(off[count] - off[0])
+        dst = torch.zeros(n + 64, dtype=torch.uint8, device=self._dev)
+        d_ids = torch.from_numpy(ids.view(np.int32).copy()).to(self._dev)
+        torch.cuda.synchronize()
+        rc = self.engine.decode_frame_list_dev(self._comp, self.comp_size, self._dev_u64(self._c_off), self._dev_u64(self._d_off), d_ids,
+                                               self._dev_u64(off - off[0]), count, dst, n, True)
+        if rc != 0:
+            self.engine._raise(rc)
+        return dst[:n].cpu().numpy().tobytes()
+
+    def close(self):
+        self.index.close()
