@@ -130,9 +130,12 @@ enum {
                                         * provokes.  Like ZK_CHOICE_TRAIN_TRIAL_KIB it lets small inputs reach the rule's rare path */
     ZK_CHOICE_DEDUP_SLICE_KIB = 21,    /* zk_encode_dedup*: KiB of unique frames gathered into engine scratch and encoded at a time, whole frames, one at
                                         * least (1..2^22; 0 = 2^20, 1 GiB).  The bytes do not depend on it; the scratch does */
-    ZK_CHOICE_DEDUP_PASS_KIB = 22      /* zk_dedup_against_dev / zk_encode_dedup_against_dev / zk_dedup_index_add_archive_dev: KiB of archive frames decoded
+    ZK_CHOICE_DEDUP_PASS_KIB = 22,     /* zk_dedup_against_dev / zk_encode_dedup_against_dev / zk_dedup_index_add_archive_dev: KiB of archive frames decoded
                                         * into engine scratch at a time, whole frames, one at least (1..2^22; 0 = 2^20, 1 GiB).  The results do not
                                         * depend on it; the scratch does */
+    ZK_CHOICE_COMPACT_SLICE_KIB = 23   /* zk_compact_archive_dev in place: KiB of the destination moved per step, in whole tiles of 64 KiB, one at least
+                                        * (1..2^22; 0 = 2^18, 256 MiB).  The bytes do not depend on it; the scratch (a staged step's bytes) and the
+                                        * number of steps do.  It lets small inputs take many steps */
 };
 int zk_engine_set_kernel_choice(zk_engine *e, int what, int value);
 /* Frames of the last finished device-pointer decode (zk_decode_frames_dev and its siblings, zk_decode_wait) whose Content_Checksum was
@@ -329,6 +332,9 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *   zk_dedup_against_dev, zk_encode_dedup_against_dev,                              refused   served    refused    (the candidates are decoded on context 0;
  *     zk_dedup_index_add_archive_dev                                                                                *n_fresh, the arrays and the index stay)
  *   zk_dedup_index_create / _free / _count / _add[_dev] / _export / _truncate,      served    served    served     (memory of the index's own, the encoder's scratch)
+ *   zk_mark_frames_dev, zk_compact_archive_dev, zk_remap_ids_dev,                   served    served    served     (the encoder's scratch and the index's own memory, no decode
+ *     zk_dedup_index_compact_dev                                                                                    context.  Compacting an archive that a submitted batch is reading
+ *                                                                                                                   breaks that batch's "buffers stay untouched" rule: the caller's business)
  *     zk_frame_keys[_dev]
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
@@ -657,8 +663,7 @@ int zk_encode_dedup(zk_engine *e, const uint8_t *src, const uint64_t *off, uint3
  * from c_sizes / d_sizes (or calls zk_dedup_index_truncate when it cannot).  There is no prefix route: the verifying decode takes no prefix, so
  * the call has no prefix parameters.  cdict is allowed; the verification of later calls then needs the matching dictionary set on the engine
  * (zk_engine_set_dictionary), which is the caller's business.
- * Not here: Level-B handles, host-pointer forms of the two `against` calls, an on-disk container for ids or for an exported index, removing
- * frames from an archive. */
+ * Not here: Level-B handles, host-pointer forms of the two `against` calls, an on-disk container for ids or for an exported index. */
 typedef struct zk_dedup_index zk_dedup_index;
 zk_dedup_index *zk_dedup_index_create(zk_engine *e);
 void zk_dedup_index_free(zk_dedup_index *x);
@@ -680,6 +685,52 @@ int zk_encode_dedup_against_dev(zk_engine *e, zk_dedup_index *x,
                                 const void *d_src, const void *d_off, uint32_t count, int level, int checksum, const zk_cdict *cdict,
                                 void *d_dst, uint64_t dst_cap, void *d_ids, void *d_fresh, void *d_c_sizes, void *d_d_sizes,
                                 uint32_t *n_fresh, uint64_t *written, void *stream);
+
+/* ---- Frames removed from a device-resident archive: a backup whose oldest snapshot is dropped, a chunk store with retention.  The reference
+ * has no counterpart.  The ARCHIVE is what zk_decode_frame_list_dev reads: d_comp, comp_size, d_c_off[n_frames + 1], d_d_off[n_frames + 1]
+ * (uint64, non-decreasing).  live[n_frames] is uint8, nonzero = keep.  THE RULE, a pure function of these:
+ *   - kept[0 .. n_kept) is the ascending list of s with live[s] != 0
+ *   - remap[s] is the position of s in kept, or ZK_FRAME_REMOVED for a removed frame
+ *   - c_off_out[0] = c_off[0], d_off_out[0] = d_off[0]; c_off_out[k + 1] - c_off_out[k] is the compressed size of frame kept[k], and the same
+ *     holds for d_off_out
+ *   - dst[c_off_out[k], c_off_out[k + 1]) is, byte for byte, comp[c_off[kept[k]], c_off[kept[k] + 1])
+ *   - *written = c_off_out[n_kept]: one past the last byte of the compacted archive, counted from d_dst, like comp_size
+ * Kept frames keep their order, so the "smallest archive frame" of zk_dedup_against_dev over the compacted archive is what the rule gives over
+ * the kept frames.  No frame is decoded: the call moves bytes and never looks inside them.  Entries of compressed size 0 are legal, kept or
+ * removed.
+ * zk_mark_frames_dev sets live[ids[i]] = 1 for count uint32 ids.  It only sets: the caller zeroes live once and marks every snapshot it keeps,
+ * call after call.  An id at or above n_frames returns ZK_ERR_ARGUMENT and leaves live as it was (the ids are checked first, then written;
+ * one wait between).  count == 0 returns 0.
+ * zk_compact_archive_dev writes remap (uint32, n_frames entries), c_off_out and d_off_out (uint64, n_kept + 1 entries; size them for n_frames
+ * + 1); each may be NULL.  *n_kept and *written are always set.  d_dst may be d_comp itself: IN PLACE, the form a store uses; otherwise
+ * d_dst[0, dst_cap) must not overlap d_comp[0, comp_size + ZK_COMP_PADDING): any other overlap is ZK_ERR_ARGUMENT.  The offsets may be updated
+ * in place too (d_c_off_out == d_c_off, d_d_off_out == d_d_off).  Nothing is stored outside dst[c_off[0], written); in place nothing before
+ * the first removed frame is stored at all, and nothing at or beyond written.  Nothing is loaded outside comp[c_off[0], c_off[n_frames]).
+ *   - dst_cap < written (out of place; in place dst_cap is not looked at) returns -70 with the destination and the arrays untouched,
+ *     *n_kept = 0 and *written = the size that is needed
+ *   - a decreasing offset list, c_off[n_frames] > comp_size, NULL d_live or d_dst return ZK_ERR_ARGUMENT
+ *   - n_frames > ZK_SEEKABLE_MAX_FRAMES returns ZK_ERR_FRAME_INDEX_TOO_LARGE before anything is read
+ *   - n_frames == 0 returns 0 with *n_kept = 0 and *written = c_off[0] if d_c_off is given, else 0
+ *   - a refused call writes nothing
+ * It SYNCHRONISES ITS STREAM once for the checks and the totals, and at the end.  In place the bytes move in steps of
+ * ZK_CHOICE_COMPACT_SLICE_KIB destination bytes from the first removed frame on; a step that cannot read and write side by side goes through
+ * engine scratch of one step's size.
+ * zk_remap_ids_dev: ids_out[i] = remap[ids[i]] (uint32; d_ids_out may be d_ids).  An id at or above n_frames, or one of a removed frame,
+ * returns ZK_ERR_ARGUMENT and leaves ids_out untouched.
+ * zk_dedup_index_compact_dev: the index after the same removal.  n_frames must equal zk_dedup_index_count(x) and remap must be what
+ * zk_compact_archive_dev writes (kept frames numbered 0, 1, ... in order), else ZK_ERR_ARGUMENT.  The keys and lengths of the kept frames move
+ * to their new places on the device and the table is rebuilt from them as zk_dedup_index_truncate rebuilds it; m becomes n_kept.  The index
+ * then behaves exactly like one built by zk_dedup_index_add from the kept frames' exported keys and sizes.  Nothing is decoded.  On any
+ * refusal the index is unchanged.
+ * Not here: merging duplicate frames an archive already holds, host-pointer forms, Level-B handles, re-encoding kept frames, compaction
+ * across several archives. */
+#define ZK_FRAME_REMOVED 0xFFFFFFFFu
+int zk_mark_frames_dev(zk_engine *e, const void *d_ids, uint32_t count, uint32_t n_frames, void *d_live, void *stream);
+int zk_compact_archive_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off, uint32_t n_frames,
+                           const void *d_live, void *d_dst, uint64_t dst_cap, void *d_c_off_out, void *d_d_off_out, void *d_remap,
+                           uint32_t *n_kept, uint64_t *written, void *stream);
+int zk_remap_ids_dev(zk_engine *e, const void *d_remap, uint32_t n_frames, const void *d_ids, uint32_t count, void *d_ids_out, void *stream);
+int zk_dedup_index_compact_dev(zk_dedup_index *x, const void *d_remap, uint32_t n_frames, void *stream);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside

@@ -136,6 +136,10 @@ _sig = {
     "zk_dedup_against_dev": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), _P]),
     "zk_encode_dedup_against_dev": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_int, C.c_int, _P, _P, C.c_uint64,
                                               _P, _P, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
+    "zk_mark_frames_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "zk_compact_archive_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
+    "zk_remap_ids_dev": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, _P]),
+    "zk_dedup_index_compact_dev": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

@@ -460,3 +460,16 @@ extern "C" int zk_encode_dedup_against_dev(zk_engine *e, zk_dedup_index *x, cons
     if (written) *written = wr;
     return 0;
 }
+
+// zk_dedup_index_compact_dev (zk_compact.hip) moves the kept frames' keys and lengths to the front of the arrays and has the table rebuilt here
+ZkDxArrays zk_dedup_index_arrays(zk_dedup_index *x) { return ZkDxArrays{x->e, x->m, x->keys, x->lens}; }
+int zk_dedup_index_rebuilt(zk_dedup_index *x, hipStream_t st, uint32_t m)
+{
+    zk_engine *e = x->e;
+    x->m = m;
+    if (const int rc = zkx_rebuild(x, st, m)) return rc;
+    ZK_HIP(hipStreamSynchronize(st));
+    ZK_HIP(hipGetLastError());
+    zk_profile_collect(e);
+    return 0;
+}

@@ -12,7 +12,8 @@ enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_
        ZK_K_RANGE_PLAN, ZK_K_RANGE_PIECES, ZK_K_RANGE_GATHER, ZK_K_RANGE_STATUS,
        ZK_K_TRAIN_COUNT, ZK_K_TRAIN_SELECT, ZK_K_TRAIN_STATS, ZK_K_CDC_MARK, ZK_K_CDC_SELECT,
        ZK_K_DEDUP_HASH, ZK_K_DEDUP_INSERT, ZK_K_DEDUP_VERIFY, ZK_K_DEDUP_VERIFY_LONG, ZK_K_DEDUP_COMPACT, ZK_K_DEDUP_GATHER,
-       ZK_K_DXI_INSERT, ZK_K_DXI_LOOKUP, ZK_K_DXI_COMPARE, ZK_K_DXI_EMIT, ZK_NKERNELS };
+       ZK_K_DXI_INSERT, ZK_K_DXI_LOOKUP, ZK_K_DXI_COMPARE, ZK_K_DXI_EMIT,
+       ZK_K_CMP_MARK, ZK_K_CMP_EMIT, ZK_K_CMP_MOVE, ZK_K_CMP_REMAP, ZK_K_CMP_TAKE, ZK_NKERNELS };
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };
@@ -92,10 +93,12 @@ struct zk_engine {
         zk_devbuf dd, dd_src, dd_off, dd_dry, dd_up, dd_out;    // zk_dedup_frames* / zk_encode_dedup* (zk_dedup.hip): the map's scratch (ZkDedupLayout); a gathered slice of unique frames and its offsets; a slice encoded for its size only; the host entry points' upload of source and offsets, and their outputs
         uint8_t *pin_dd = nullptr; size_t pin_dd_cap = 0;     // ... the caller's offsets and the unique frames' indices, brought to the host
         zk_devbuf dx;                       // zk_dedup_against_dev / zk_encode_dedup_against_dev (zk_dedup_index.hip): the lookup's scratch (ZkDxLayout); the decoded candidates of a pass lie in dctx[0].rng
+        zk_devbuf cmp, cmp_gaps, cmp_stage; // zk_compact_archive_dev and its siblings (zk_compact.hip): the scratch (ZkCmpLayout); the gaps of an in-place compaction's steps; a staged step's bytes
         int plan_choice = 0;                // ZK_CHOICE_ENC_PLAN
         uint32_t dedup_key_bits = 0;        // zk_dedup_frames*: bits of a frame's key that are kept (0 = all 64), ZK_CHOICE_DEDUP_KEY_BITS
         uint64_t dedup_slice_bytes = 0;     // zk_encode_dedup*: bytes of unique frames gathered and encoded at a time (0 = 1 GiB), ZK_CHOICE_DEDUP_SLICE_KIB
         uint64_t dedup_pass_bytes = 0;      // zk_dedup_against_dev, zk_dedup_index_add_archive_dev: decoded bytes of archive frames held at a time (0 = 1 GiB), ZK_CHOICE_DEDUP_PASS_KIB
+        uint64_t compact_slice_bytes = 0;   // zk_compact_archive_dev in place: destination bytes moved per step (0 = 256 MiB), ZK_CHOICE_COMPACT_SLICE_KIB
         uint64_t cdc_slice_bytes = 0;       // zk_chunk_boundaries*: input bytes whose candidates are held at a time (0 = 64 MiB), ZK_CHOICE_CDC_SLICE_KIB
         uint64_t train_trial_bytes = 0;     // zk_train_dictionary*: sample bytes the candidates are tried on (0 = 64 MiB), ZK_CHOICE_TRAIN_TRIAL_KIB
         uint64_t dense_slice_bytes = 0;     // input bytes the dense scratch is reserved for (0 = 4 GiB), ZK_CHOICE_ENC_DENSE_SLICE_KIB
@@ -164,6 +167,12 @@ int zk_dec_exec_checksums(zk_engine *e, zk_engine::DecCtx &c, hipStream_t st, co
 // with this, before it reserves, uploads or waits for anything
 inline bool zk_batch_outstanding(const zk_engine *e) { return e->slot_busy[0] || e->slot_busy[1]; }
 inline bool zk_dict_applies(const zk_engine *e, const void *d_prefix) { return e->dict.on && !d_prefix; }
+// what zk_dedup_index_compact_dev (zk_compact.hip) reaches the index through (zk_dedup_index.hip): its arrays, and the table rebuilt for m
+// frames whose keys and lengths are in place (zk_dedup_index_truncate's path; the stream is synchronised)
+struct zk_dedup_index;
+struct ZkDxArrays { zk_engine *e; uint32_t m; uint64_t *keys; uint32_t *lens; };
+ZkDxArrays zk_dedup_index_arrays(zk_dedup_index *x);
+int zk_dedup_index_rebuilt(zk_dedup_index *x, hipStream_t st, uint32_t m);
 namespace zeekstd { class SeekTable; }
 struct zk_seek_table;
 zk_seek_table *zk_seek_table_from_cpp(const zeekstd::SeekTable *t);

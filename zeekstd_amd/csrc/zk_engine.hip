@@ -61,7 +61,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     if (!e) return ZK_ERR_ARGUMENT;
     ZkKernelChoice &k = e->choice;
     switch (what) {
-    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; e->range_pass_bytes = 0; e->enc.dense_slice_bytes = 0; e->enc.dict_slice_bytes = 0; e->enc.plan_choice = 0; e->enc.train_trial_bytes = 0; e->enc.cdc_slice_bytes = 0; e->enc.dedup_key_bits = 0; e->enc.dedup_slice_bytes = 0; e->enc.dedup_pass_bytes = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
+    case ZK_CHOICE_RESET: k = ZkKernelChoice(); e->pipe_contexts = 0; e->pipe_chunk_bytes = 0; e->range_pass_bytes = 0; e->enc.dense_slice_bytes = 0; e->enc.dict_slice_bytes = 0; e->enc.plan_choice = 0; e->enc.train_trial_bytes = 0; e->enc.cdc_slice_bytes = 0; e->enc.dedup_key_bits = 0; e->enc.dedup_slice_bytes = 0; e->enc.dedup_pass_bytes = 0; e->enc.compact_slice_bytes = 0; zk_hostpipe_tune(e); return 0;   // every key, the host pipeline's two included
     case ZK_CHOICE_FSE_OWN: if (value < 0 || value > 2) return ZK_ERR_ARGUMENT; k.fse_own = value; return 0;
     case ZK_CHOICE_FSE_SHARED: if (value < 0 || value > 3) return ZK_ERR_ARGUMENT; k.fse_shared = value; return 0;
     case ZK_CHOICE_EXEC_LANES: if (value != 0 && value != 128 && value != 256 && value != 512 && value != 1024) return ZK_ERR_ARGUMENT; k.exec_lanes = value; return 0;
@@ -84,6 +84,7 @@ extern "C" int zk_engine_set_kernel_choice(zk_engine *e, int what, int value)
     case ZK_CHOICE_DEDUP_KEY_BITS: if (value < 0 || value > 64) return ZK_ERR_ARGUMENT; e->enc.dedup_key_bits = (uint32_t)value; return 0;
     case ZK_CHOICE_DEDUP_SLICE_KIB: if (value < 0 || value > (1 << 22)) return ZK_ERR_ARGUMENT; e->enc.dedup_slice_bytes = (uint64_t)value << 10; return 0;
     case ZK_CHOICE_DEDUP_PASS_KIB: if (value < 0 || value > (1 << 22)) return ZK_ERR_ARGUMENT; e->enc.dedup_pass_bytes = (uint64_t)value << 10; return 0;
+    case ZK_CHOICE_COMPACT_SLICE_KIB: if (value < 0 || value > (1 << 22)) return ZK_ERR_ARGUMENT; e->enc.compact_slice_bytes = (uint64_t)value << 10; return 0;
     default: return ZK_ERR_ARGUMENT;
     }
 }
@@ -99,7 +100,8 @@ extern "C" const char *zk_engine_kernel_name(int k)
                                              "zk_k_train_count", "zk_k_train_select", "zk_k_train_stats",
                                              "zk_k_cdc_mark", "zk_k_cdc_select",
                                              "zk_k_dedup_hash", "zk_k_dedup_insert", "zk_k_dedup_verify", "zk_k_dedup_verify_long", "zk_k_dedup_compact", "zk_k_dedup_gather",
-                                             "zk_k_dxi_insert", "zk_k_dxi_lookup", "zk_k_dxi_compare", "zk_k_dxi_emit"};
+                                             "zk_k_dxi_insert", "zk_k_dxi_lookup", "zk_k_dxi_compare", "zk_k_dxi_emit",
+                                             "zk_k_cmp_mark", "zk_k_cmp_emit", "zk_k_cmp_move", "zk_k_cmp_remap_ids", "zk_k_cmp_take"};
     return k >= 0 && k < ZK_NKERNELS ? names[k] : "";
 }
 extern "C" int zk_engine_kernel_times(const zk_engine *e, float *ms_out, int n)
@@ -182,7 +184,7 @@ extern "C" void zk_engine_destroy(zk_engine *e)
     for (auto &c : e->dctx) if (c.st) (void)hipStreamSynchronize(c.st);
     zk_devbuf *bufs[] = {&e->dict.buf, &e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc, &e->rf_entries, &e->rf_frames,
                          &e->enc.lists, &e->enc.seqs, &e->enc.lits, &e->enc.scratch, &e->enc.words, &e->enc.ftab, &e->enc.hist, &e->enc.seg, &e->enc.ldm, &e->enc.dense, &e->enc.plan, &e->enc.train, &e->enc.train_src, &e->enc.cdc, &e->enc.cdc_src, &e->enc.cdc_off,
-                         &e->enc.dd, &e->enc.dd_src, &e->enc.dd_off, &e->enc.dd_dry, &e->enc.dd_up, &e->enc.dd_out, &e->enc.dx};
+                         &e->enc.dd, &e->enc.dd_src, &e->enc.dd_off, &e->enc.dd_dry, &e->enc.dd_up, &e->enc.dd_out, &e->enc.dx, &e->enc.cmp, &e->enc.cmp_gaps, &e->enc.cmp_stage};
     for (zk_devbuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (e->h_words) (void)hipHostFree(e->h_words);
     for (int k = 0; k < ZK_NKERNELS; k++) { if (e->ev_start[k]) (void)hipEventDestroy(e->ev_start[k]); if (e->ev_stop[k]) (void)hipEventDestroy(e->ev_stop[k]); }

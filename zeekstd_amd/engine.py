@@ -124,7 +124,7 @@ class Engine:
     CHOICES = {"reset": 0, "fse_own": 1, "fse_shared": 2, "exec_lanes": 3, "exec_ring": 4, "xxh64": 5, "small_path": 6,
                "pipe_contexts": 7, "pipe_chunk_mib": 8, "exec_resident": 9, "exec_seg": 10, "seg_kib": 11, "seg_fill": 12,
                "entropy": 13, "range_pass_mib": 14, "enc_dense_slice_kib": 15, "enc_dict_slice_kib": 16, "enc_plan": 17, "train_trial_kib": 18,
-               "cdc_slice_kib": 19, "dedup_key_bits": 20, "dedup_slice_kib": 21, "dedup_pass_kib": 22}
+               "cdc_slice_kib": 19, "dedup_key_bits": 20, "dedup_slice_kib": 21, "dedup_pass_kib": 22, "compact_slice_kib": 23}
 
     def frame_content_sizes(self, comp: bytes, c_off, first=0, count=None):
         """zk_frame_content_sizes: the decompressed sizes of frames nobody holds seek entries for (header walk + sequence walks on the device,
@@ -493,6 +493,35 @@ class Engine:
             self._raise(rc)
         return nf.value, wr.value
 
+    def mark_frames_dev(self, d_ids, count, n_frames, d_live, stream=None):
+        """zk_mark_frames_dev: live[ids[i]] = 1 for `count` uint32 ids (device tensors or raw pointers); d_live: n_frames uint8 flags, zeroed by
+        the caller before the first snapshot it keeps is marked"""
+        rc = lib.zk_mark_frames_dev(self._h, self._ptr(d_ids), count, n_frames, self._ptr(d_live), stream)
+        if rc != 0:
+            self._raise(rc)
+
+    def compact_archive_dev(self, d_comp, comp_size, d_c_off, d_d_off, n_frames, d_live, d_dst, dst_cap, d_c_off_out=None, d_d_off_out=None,
+                            d_remap=None, stream=None, raise_on_error=True):
+        """zk_compact_archive_dev: the frames with live[s] != 0, in order and back to back in d_dst (d_dst may be d_comp: in place).  d_c_off_out /
+        d_d_off_out: uint64 arrays of n_frames + 1 entries, d_remap: uint32 of n_frames, or None.  Returns (n_kept, written); with
+        raise_on_error=False (rc, n_kept, written)."""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        nk = C.c_uint32()
+        wr = C.c_uint64()
+        rc = lib.zk_compact_archive_dev(self._h, opt(d_comp), comp_size, opt(d_c_off), opt(d_d_off), n_frames, opt(d_live), opt(d_dst), dst_cap,
+                                        opt(d_c_off_out), opt(d_d_off_out), opt(d_remap), C.byref(nk), C.byref(wr), stream)
+        if not raise_on_error:
+            return rc, nk.value, wr.value
+        if rc != 0:
+            self._raise(rc)
+        return nk.value, wr.value
+
+    def remap_ids_dev(self, d_remap, n_frames, d_ids, count, d_ids_out=None, stream=None):
+        """zk_remap_ids_dev: ids_out[i] = remap[ids[i]] (d_ids_out None: in place)"""
+        rc = lib.zk_remap_ids_dev(self._h, self._ptr(d_remap), n_frames, self._ptr(d_ids), count, self._ptr(d_ids_out if d_ids_out is not None else d_ids), stream)
+        if rc != 0:
+            self._raise(rc)
+
     @staticmethod
     def _train_params(k, d, f, level, dict_id, raw_content):
         return _lib.TrainParams(k, d, f, level, dict_id, _lib.TRAIN_RAW_CONTENT if raw_content else 0)
@@ -686,6 +715,10 @@ class DedupIndex:
     def truncate(self, count):
         self._check(lib.zk_dedup_index_truncate(self._h, count))
 
+    def compact_dev(self, d_remap, n_frames, stream=None):
+        """the index after the removal zk_compact_archive_dev made: d_remap as that call wrote it, n_frames == count"""
+        self._check(lib.zk_dedup_index_compact_dev(self._h, Engine._ptr(d_remap), n_frames, stream))
+
     def close(self):
         if getattr(self, "_h", None):
             if self._engine._h:
@@ -701,7 +734,8 @@ class DedupIndex:
 
 class DedupStore:
     """A growing device-resident archive and its DedupIndex: append() stores the chunks the archive does not hold yet, read() returns any
-    list of chunks.  Python over the device calls only (chunk_boundaries_dev, encode_dedup_against_dev, decode_frame_list_dev)."""
+    list of chunks, compact() drops the chunks no kept snapshot uses.  Python over the device calls only (chunk_boundaries_dev,
+    encode_dedup_against_dev, decode_frame_list_dev, mark_frames_dev, compact_archive_dev, remap_ids_dev)."""
 
     def __init__(self, engine, level=1, checksum=True, dictionary=None):
         import torch
@@ -768,6 +802,33 @@ class DedupStore:
         if rc != 0:
             self.engine._raise(rc)
         return dst[:n].cpu().numpy().tobytes()
+
+    def compact(self, keep):
+        """Drops every chunk that none of the snapshots in `keep` (a list of `ids` arrays, as append returned them) uses: the archive is
+        compacted in place, the index with it.  Returns the renumbered ids arrays in the same order; read() with them returns what it
+        returned before."""
+        import torch
+        n = self.n_frames
+        keep = [np.ascontiguousarray(np.asarray(k, dtype=np.uint32)) for k in keep]
+        if n == 0:
+            return keep
+        live = torch.zeros(n, dtype=torch.uint8, device=self._dev)
+        d_keep = [torch.from_numpy(k.view(np.int32).copy()).to(self._dev) for k in keep]
+        d_c, d_d = self._dev_u64(self._c_off), self._dev_u64(self._d_off)
+        remap = torch.zeros(n, dtype=torch.int32, device=self._dev)
+        torch.cuda.synchronize()
+        for k, d in zip(keep, d_keep):
+            if len(k):
+                self.engine.mark_frames_dev(d, len(k), n, live)
+        nk, wr = self.engine.compact_archive_dev(self._comp, self.comp_size, d_c, d_d, n, live, self._comp, self._comp.numel(), d_c, d_d, remap)
+        for k, d in zip(keep, d_keep):
+            if len(k):
+                self.engine.remap_ids_dev(remap, n, d, len(k))
+        self.index.compact_dev(remap, n)
+        self._c_off = d_c[:nk + 1].cpu().numpy().view(np.uint64).copy()
+        self._d_off = d_d[:nk + 1].cpu().numpy().view(np.uint64).copy()
+        self.comp_size = wr
+        return [d.cpu().numpy().view(np.uint32).copy() for d in d_keep]
 
     def close(self):
         self.index.close()
