@@ -108,7 +108,7 @@ enum {
     ZK_CHOICE_ENTROPY = 13,       /* literals and sequences of a device-pointer batch: 1 = zk_k_huf beside the sequence kernels on two queues, 2 = one kernel
                                    * (zk_k_entropy_frame) for every batch that qualifies -- no frame with more than one set of own tables -- whatever its
                                    * size; 0 = by batch shape.  zk_engine_entropy_fused says which one ran */
-    ZK_CHOICE_RANGE_PASS_MIB = 14, /* zk_read_ranges*: decoded MiB of scratch per pass (1..2^20; 0 = 1024).  A pass is never less than one frame */
+    ZK_CHOICE_RANGE_PASS_MIB = 14, /* zk_read_ranges*, zk_read_view_ranges_dev: decoded MiB of scratch per pass (1..2^20; 0 = 1024).  A pass is never less than one frame */
     ZK_CHOICE_ENC_DENSE_SLICE_KIB = 15, /* encodes with dense far history (level 0 / >= 3, frames beyond the matcher's ring): input KiB whose candidate scratch
                                         * (8 bytes per input byte) is reserved at a time (1..2^22; 0 = 2^22, 4 GiB).  A longer input is matched slice after
                                         * slice of whole frames over that scratch, never less than one frame; the bytes produced do not depend on it */
@@ -202,8 +202,37 @@ int zk_read_ranges_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, con
 int zk_read_ranges(zk_engine *e, const uint8_t *comp, uint64_t comp_size, const uint64_t *c_off, const uint64_t *d_off, uint32_t n_frames,
                    const uint64_t *offs, const uint64_t *lens, const uint64_t *dst_off, uint32_t count,
                    uint8_t *dst, uint64_t dst_cap, int verify, int32_t *range_status);
-/* Frames the last zk_read_ranges* call decoded (every touched frame once).  A diagnostic. */
+/* Frames the last zk_read_ranges* / zk_read_view_ranges_dev call decoded (every touched frame once).  A diagnostic. */
 uint64_t zk_engine_ranges_frames_decoded(const zk_engine *e);
+
+/* Batched reads of a VIEW of a device-resident archive: what a chunk store keeps of a snapshot.  A view is d_view_ids[view_count] (uint32
+ * archive frames, any order, repeats allowed) and d_view_off[view_count + 1] (uint64, non-decreasing; d_view_off[0] need not be 0) -- the
+ * ids / off pair zk_dedup_frames, zk_encode_dedup[_against]_dev and DedupStore.append return.
+ * THE RULE, a pure function of the decoded archive frames, the view and the ranges:
+ *   - the view's stream is the decoded bytes of frame view_ids[0], then view_ids[1], ...: the byte at coordinate view_off[j] + p is byte p
+ *     of the decoded archive frame view_ids[j].
+ *   - range i is [d_offs[i], d_offs[i] + d_lens[i]) in the coordinates of view_off and lands at d_dst + d_dst_off[i]; d_dst_off == NULL packs
+ *     the ranges in list order (a range outside the stream takes no room).  Ranges may overlap, repeat, be empty, come in any order, cross
+ *     any number of entries and exceed 4 GiB, as the stream may.  An offset on an entry boundary belongs to the entry that starts there and
+ *     empty entries are skipped (zk_read_ranges_dev's edge rule, over view_off).
+ *   - the view is checked WHOLE before anything is decoded or written, whether a range touches an entry or not: every view_ids[j] < n_frames,
+ *     view_off non-decreasing, view_off[j + 1] - view_off[j] == d_off[view_ids[j] + 1] - d_off[view_ids[j]].  Anything else: ZK_ERR_ARGUMENT,
+ *     d_dst and d_range_status untouched.
+ *   - d_range_status (optional, int32, count entries): 0; ZK_ERR_OFFSET_OUT_OF_RANGE for a range that leaves [view_off[0],
+ *     view_off[view_count]] or whose off + len overflows; -70 (dstSize_tooSmall) for one whose destination leaves dst_cap -- such a range
+ *     writes nothing, its neighbours are served --; or -(ZSTD_ErrorCode) of the first entry, in VIEW order, that it touches and whose frame
+ *     failed to decode or verify -- its bytes are then unspecified within its own destination, the other ranges are delivered all the same.
+ *   - exactly the bytes of the good ranges are written: nothing between or behind the destinations.
+ *   - every archive frame is decoded AT MOST ONCE per call, however many entries name it and however many ranges touch those entries, into
+ *     scratch of the engine bounded by ZK_CHOICE_RANGE_PASS_MIB (passes are slices of the sorted list of distinct frames, one frame at least);
+ *     frames that no touched, non-empty entry names are not decoded.  zk_engine_ranges_frames_decoded: the distinct frames decoded.
+ *   - verify, an engine dictionary, ZK_COMP_PADDING and `stream` as for zk_read_ranges_dev.  There is no prefix mode.  count == 0 returns 0.
+ * Returns 0, or the status of the first failing range in list order; engine errors as everywhere.  With the identity view (view_ids = 0 ..
+ * n_frames - 1, view_off = d_off) the call is zk_read_ranges_dev: same bytes, statuses, return value and frame count. */
+int zk_read_view_ranges_dev(zk_engine *e, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off, uint32_t n_frames,
+                            const void *d_view_ids, const void *d_view_off, uint32_t view_count,
+                            const void *d_offs, const void *d_lens, const void *d_dst_off, uint32_t count,
+                            void *d_dst, uint64_t dst_cap, int verify, void *d_range_status, void *stream);
 
 /* Decode with a raw-content prefix (patch mode): what the reference does with ZSTD_DCtx_refPrefix before the first
  * frame and again after every frame end (lib/src/decode.rs:212-214, 248-255) -- every frame of the batch sees the
@@ -310,7 +339,7 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *
  *                                                                                   (a)       (b)       (c)
  *   zk_decode_frames_dev, zk_decode_frames_prefix_dev, zk_decode_frame_list_dev     refused   served    refused    (they run on context 0,
- *   zk_frame_content_sizes_dev, zk_read_ranges_dev                                  refused   served    refused     also on the caller's stream)
+ *   zk_frame_content_sizes_dev, zk_read_ranges_dev, zk_read_view_ranges_dev         refused   served    refused     also on the caller's stream)
  *   zk_frame_content_sizes, zk_read_ranges (host pointers)                          refused   served    refused
  *   zk_refine_entries_dev, zk_refine_entries                                        refused   served    refused    (context 0; *n_out and the arrays stay)
  *   zk_decode_frames, zk_decode_frames_prefix, zk_decode_shard (host pipeline)      refused   refused   refused    (it rotates through both contexts)
@@ -596,7 +625,8 @@ int zk_encode_chunked(zk_engine *e, const uint8_t *src, uint64_t n, const zk_chu
  * twice, the first time into scratch).  The host-pointer call uploads the source whole and stages the prefix as zk_encode_frame_list does.
  * READING BACK needs nothing new.  With c_off / d_off the prefix sums of the n_unique c_sizes / d_sizes,
  *     zk_decode_frame_list_dev(e, d_comp, written, d_c_off, d_d_off, d_ids = ids, d_out_off = off - off[0], count, d_dst, off[count] - off[0], ...)
- * reproduces src[off[0], off[count]): ids may repeat and come in any order.  Where ids is kept is the caller's business (a skippable frame
+ * reproduces src[off[0], off[count]): ids may repeat and come in any order.  zk_read_view_ranges_dev(..., d_view_ids = ids, d_view_off = off,
+ * view_count = count, ...) reads any byte ranges of src[off[0], off[count]) instead, and decodes a frame that ids names several times once.  Where ids is kept is the caller's business (a skippable frame
  * is the obvious place); nothing is remembered from call to call -- that is what zk_dedup_index and zk_encode_dedup_against_dev, below, are for. */
 int zk_dedup_frames_dev(zk_engine *e, const void *d_src, const void *d_off, uint32_t count,
                         void *d_ref, void *d_ids, void *d_uniq, uint32_t *n_unique, void *stream);

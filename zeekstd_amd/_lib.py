@@ -79,6 +79,7 @@ _sig = {
     "zk_read_ranges_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P, _P]),
     "zk_read_ranges": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P]),
     "zk_engine_ranges_frames_decoded": (C.c_uint64, [_P]),
+    "zk_read_view_ranges_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P, _P]),
     "zk_xxh64_frames": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "zk_host_alloc": (_P, [C.c_size_t]),
     "zk_host_free": (None, [_P]),

@@ -13,7 +13,8 @@ enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_
        ZK_K_TRAIN_COUNT, ZK_K_TRAIN_SELECT, ZK_K_TRAIN_STATS, ZK_K_CDC_MARK, ZK_K_CDC_SELECT,
        ZK_K_DEDUP_HASH, ZK_K_DEDUP_INSERT, ZK_K_DEDUP_VERIFY, ZK_K_DEDUP_VERIFY_LONG, ZK_K_DEDUP_COMPACT, ZK_K_DEDUP_GATHER,
        ZK_K_DXI_INSERT, ZK_K_DXI_LOOKUP, ZK_K_DXI_COMPARE, ZK_K_DXI_EMIT,
-       ZK_K_CMP_MARK, ZK_K_CMP_EMIT, ZK_K_CMP_MOVE, ZK_K_CMP_REMAP, ZK_K_CMP_TAKE, ZK_NKERNELS };
+       ZK_K_CMP_MARK, ZK_K_CMP_EMIT, ZK_K_CMP_MOVE, ZK_K_CMP_REMAP, ZK_K_CMP_TAKE,
+       ZK_K_VIEW_PLAN, ZK_K_VIEW_MARK, ZK_K_VIEW_GATHER, ZK_K_VIEW_STATUS, ZK_NKERNELS };
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };

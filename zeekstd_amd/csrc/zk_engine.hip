@@ -101,7 +101,8 @@ extern "C" const char *zk_engine_kernel_name(int k)
                                              "zk_k_cdc_mark", "zk_k_cdc_select",
                                              "zk_k_dedup_hash", "zk_k_dedup_insert", "zk_k_dedup_verify", "zk_k_dedup_verify_long", "zk_k_dedup_compact", "zk_k_dedup_gather",
                                              "zk_k_dxi_insert", "zk_k_dxi_lookup", "zk_k_dxi_compare", "zk_k_dxi_emit",
-                                             "zk_k_cmp_mark", "zk_k_cmp_emit", "zk_k_cmp_move", "zk_k_cmp_remap_ids", "zk_k_cmp_take"};
+                                             "zk_k_cmp_mark", "zk_k_cmp_emit", "zk_k_cmp_move", "zk_k_cmp_remap_ids", "zk_k_cmp_take",
+                                             "zk_k_view_plan", "zk_k_view_mark", "zk_k_view_gather", "zk_k_view_status"};
     return k >= 0 && k < ZK_NKERNELS ? names[k] : "";
 }
 extern "C" int zk_engine_kernel_times(const zk_engine *e, float *ms_out, int n)

@@ -84,6 +84,8 @@ constexpr uint64_t ZK_RANGE_CHUNK = 64u << 10;
 // (n_frames + 1 words) must be zero.
 void zk_launch_range_plan(hipStream_t st, const ZkRangeArgs &r, uint64_t *eff, uint64_t *packed, uint32_t *rfirst, uint32_t *rlast, int32_t *status, uint32_t *cover,
                           uint32_t *slot, uint32_t *ids, uint64_t *uoff, uint64_t *words);
+// zk_k_range_compact alone, over a difference array that somebody else filled (zk_view.hip: the frames a view's touched entries name)
+void zk_launch_range_compact(hipStream_t st, const uint64_t *d_off, uint32_t n_frames, const uint32_t *cover, uint32_t *slot, uint32_t *ids, uint64_t *uoff, uint64_t *words);
 void zk_launch_range_rebase(hipStream_t st, const uint64_t *uoff, uint32_t a, uint32_t n, uint64_t *poff);
 // the pass that holds positions [a, b) of the unique list: one copy per range (copies) and the chunk prefix sums of the large ones (cnt -> coff, count + 1)
 void zk_launch_range_pieces(hipStream_t st, const ZkRangeArgs &r, const uint64_t *dst_off, const uint32_t *rfirst, const uint32_t *rlast, const uint32_t *slot,

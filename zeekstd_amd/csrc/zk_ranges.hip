@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "zk_kernels.h"
 #include "zk_ranges.h"
+#include "zk_range_copy.h"
 
 // ------------------------------------------------------------------------------------------------ plan
 __global__ __launch_bounds__(256) void zk_k_range_lens(const uint64_t *d_off, uint32_t n_frames, const uint64_t *offs, const uint64_t *lens, uint32_t count, uint64_t *eff)
@@ -130,32 +131,6 @@ __global__ __launch_bounds__(256) void zk_k_range_pieces(const uint64_t *d_off, 
     cnt[i] = c.n > ZK_RANGE_SMALL ? (c.n + ((dst_base + c.dst) & 15) + ZK_RANGE_CHUNK - 1) / ZK_RANGE_CHUNK : 0;
 }
 
-// 16 bytes as the destination sees them, from any source address (global_load_dwordx4 takes unaligned addresses)
-struct __attribute__((packed, aligned(1))) ZkU16 { uint32_t w[4]; };
-
-// n bytes src -> dst by T lanes: 16-byte stores on the destination's grid, the bytes in front of and behind it one by one.  Nothing
-// outside [dst, dst + n) is written and nothing outside [src, src + n) read.
-template <uint32_t T> __device__ __forceinline__ void zk_range_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint64_t n, uint32_t t)
-{
-    uint64_t head = (0 - (uintptr_t)dst) & 15;
-    if (head > n) head = n;
-    if (t < head) dst[t] = src[t];
-    const uint64_t n16 = (n - head) >> 4;
-    uint4 *__restrict__ o = reinterpret_cast<uint4 *>(dst + head);
-    const ZkU16 *__restrict__ s = reinterpret_cast<const ZkU16 *>(src + head);
-    uint64_t i = t;
-    for (; i + 3 * T < n16; i += 4 * T) {               // four loads in flight per lane
-        const ZkU16 v0 = s[i], v1 = s[i + T], v2 = s[i + 2 * T], v3 = s[i + 3 * T];
-        o[i] = make_uint4(v0.w[0], v0.w[1], v0.w[2], v0.w[3]);
-        o[i + T] = make_uint4(v1.w[0], v1.w[1], v1.w[2], v1.w[3]);
-        o[i + 2 * T] = make_uint4(v2.w[0], v2.w[1], v2.w[2], v2.w[3]);
-        o[i + 3 * T] = make_uint4(v3.w[0], v3.w[1], v3.w[2], v3.w[3]);
-    }
-    for (; i < n16; i += T) { const ZkU16 v = s[i]; o[i] = make_uint4(v.w[0], v.w[1], v.w[2], v.w[3]); }
-    const uint64_t done = head + (n16 << 4);
-    if (done + t < n) dst[done + t] = src[done + t];    // (fewer than 16 bytes)
-}
-
 // Workgroups [0, small_wgs): four waves, a small copy each.  The others: the 64 KiB chunks of the large copies, dealt round robin;
 // coff (count + 1 prefix sums of the copies' chunk counts) says whose chunk a number is.
 __global__ __launch_bounds__(256) void zk_k_range_gather(const uint8_t *__restrict__ scratch, uint8_t *__restrict__ dst, const ZkRangeCopy *__restrict__ copies,
@@ -215,6 +190,10 @@ void zk_launch_range_plan(hipStream_t st, const ZkRangeArgs &r, uint64_t *eff, u
     hipLaunchKernelGGL(zk_k_range_plan, grid, dim3(256), 0, st, r.d_off, r.n_frames, r.offs, r.lens, r.dst_off ? r.dst_off : packed, r.count, r.dst_cap, rfirst, rlast,
                        status, cover);
     hipLaunchKernelGGL(zk_k_range_compact, dim3(1), dim3(1024), 0, st, r.d_off, r.n_frames, cover, slot, ids, uoff, words);
+}
+void zk_launch_range_compact(hipStream_t st, const uint64_t *d_off, uint32_t n_frames, const uint32_t *cover, uint32_t *slot, uint32_t *ids, uint64_t *uoff, uint64_t *words)
+{
+    hipLaunchKernelGGL(zk_k_range_compact, dim3(1), dim3(1024), 0, st, d_off, n_frames, cover, slot, ids, uoff, words);
 }
 void zk_launch_range_rebase(hipStream_t st, const uint64_t *uoff, uint32_t a, uint32_t n, uint64_t *poff)
 {

@@ -638,6 +638,21 @@ class Engine:
             self._raise(rc)
         return rc
 
+    def read_view_ranges_dev(self, d_comp, comp_size, d_c_off, d_d_off, n_frames, d_view_ids, d_view_off, view_count, d_offs, d_lens, d_dst_off, count,
+                             d_dst, dst_cap, verify=True, d_status=None, stream=None):
+        """Batched reads of a view (zk_read_view_ranges_dev): the view's stream is the decoded archive frames d_view_ids[j] (uint32) laid out by
+        d_view_off (uint64, view_count + 1) -- the ids / offsets pair the dedup calls return --; bytes [d_offs[i], d_offs[i] + d_lens[i]) of it ->
+        d_dst + d_dst_off[i] (None: packed in list order).  Every archive frame is decoded at most once.  Returns 0 or the first failing range's
+        status; a view that does not fit the archive raises."""
+        rc = lib.zk_read_view_ranges_dev(self._h, self._ptr(d_comp), comp_size, self._ptr(d_c_off), self._ptr(d_d_off), n_frames,
+                                         self._ptr(d_view_ids) if d_view_ids is not None else None, self._ptr(d_view_off), view_count,
+                                         self._ptr(d_offs), self._ptr(d_lens), self._ptr(d_dst_off) if d_dst_off is not None else None, count,
+                                         self._ptr(d_dst) if d_dst is not None else None, dst_cap, int(verify),
+                                         self._ptr(d_status) if d_status is not None else None, stream)
+        if rc <= -1000 and rc != -1001:
+            self._raise(rc)
+        return rc
+
     def read_ranges(self, comp, c_off, d_off, offs, lens, verify=True, packed=False):
         """Batched reads from host data (zk_read_ranges) -> (list of bytes, one per range -- b"" for a range that failed validation --, int32
         status array).  packed=True: (one bytes object with the ranges back to back, uint64 offsets of count + 1 entries, status array)."""
@@ -734,8 +749,8 @@ class DedupIndex:
 
 class DedupStore:
     """A growing device-resident archive and its DedupIndex: append() stores the chunks the archive does not hold yet, read() returns any
-    list of chunks, compact() drops the chunks no kept snapshot uses.  Python over the device calls only (chunk_boundaries_dev,
-    encode_dedup_against_dev, decode_frame_list_dev, mark_frames_dev, compact_archive_dev, remap_ids_dev)."""
+    list of chunks, read_ranges() byte ranges of a snapshot, compact() drops the chunks no kept snapshot uses.  Python over the device calls only (chunk_boundaries_dev,
+    encode_dedup_against_dev, decode_frame_list_dev, read_view_ranges_dev, mark_frames_dev, compact_archive_dev, remap_ids_dev)."""
 
     def __init__(self, engine, level=1, checksum=True, dictionary=None):
         import torch
@@ -802,6 +817,31 @@ class DedupStore:
         if rc != 0:
             self.engine._raise(rc)
         return dst[:n].cpu().numpy().tobytes()
+
+    def read_ranges(self, ids, offsets, offs, lens):
+        """Byte ranges of a snapshot (ids, offsets as append returned them): [offs[i], offs[i] + lens[i]) in the coordinates of `offsets` -> a
+        list of bytes.  Only the chunks the ranges touch are decoded, each archive frame once (read_view_ranges_dev).  A range outside the
+        snapshot or a chunk that does not decode raises."""
+        import torch
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32))
+        off, offs, lens = _u64(offsets), _u64(offs), _u64(lens)
+        count = len(offs)
+        if count == 0:
+            return []
+        if len(off) != len(ids) + 1:
+            raise ValueError("offsets must have one entry more than ids")
+        at = np.zeros(count + 1, np.uint64)
+        at[1:] = np.cumsum(lens, dtype=np.uint64)
+        n = int(at[count])
+        dst = torch.zeros(n + 64, dtype=torch.uint8, device=self._dev)
+        d_ids = torch.from_numpy(ids.view(np.int32).copy()).to(self._dev) if len(ids) else None
+        torch.cuda.synchronize()
+        rc = self.engine.read_view_ranges_dev(self._comp, self.comp_size, self._dev_u64(self._c_off), self._dev_u64(self._d_off), self.n_frames, d_ids,
+                                              self._dev_u64(off), len(ids), self._dev_u64(offs), self._dev_u64(lens), self._dev_u64(at[:count]), count, dst, n, True)
+        if rc != 0:
+            self.engine._raise(rc)
+        out = dst[:n].cpu().numpy()
+        return [out[int(at[i]):int(at[i + 1])].tobytes() for i in range(count)]
 
     def compact(self, keep):
         """Drops every chunk that none of the snapshots in `keep` (a list of `ids` arrays, as append returned them) uses: the archive is
