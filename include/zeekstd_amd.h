@@ -365,6 +365,8 @@ int zk_refine_entries(zk_engine *e, const uint8_t *comp, uint64_t comp_size, con
  *     zk_dedup_index_compact_dev                                                                                    context.  Compacting an archive that a submitted batch is reading
  *                                                                                                                   breaks that batch's "buffers stay untouched" rule: the caller's business)
  *     zk_frame_keys[_dev]
+ *   zk_frame_digests[_dev]                                                          served    served    served     (the encoder's scratch)
+ *   zk_archive_digests_dev                                                          refused   served    refused    (the frames are decoded on context 0; d_digests stays)
  *   zk_xxh64_frames[_dev]                                                           served    served    served
  *   zk_engine_set_kernel_choice / _set_fse_kernel / _set_profiling /                served    served    served     (for the calls that follow: a submitted batch keeps
  *     _set_host_threads                                                                                             the plan it was enqueued with, and is never timed)
@@ -761,6 +763,56 @@ int zk_compact_archive_dev(zk_engine *e, const void *d_comp, uint64_t comp_size,
                            uint32_t *n_kept, uint64_t *written, void *stream);
 int zk_remap_ids_dev(zk_engine *e, const void *d_remap, uint32_t n_frames, const void *d_ids, uint32_t count, void *d_ids_out, void *stream);
 int zk_dedup_index_compact_dev(zk_dedup_index *x, const void *d_remap, uint32_t n_frames, void *stream);
+
+/* ---- Content digests of frames: what names a chunk between two parties -- a client that asks a remote store which chunks it lacks, a manifest, a
+ * restore that proves a chunk is the one that was stored, tools that address chunks by hash.  The frame key above is fast and order-free but not
+ * collision-resistant; it is trusted only because every match is followed by a byte-for-byte compare.  The reference has no counterpart.
+ * Frame i is src[off[i], off[i + 1]) (off[count + 1], non-decreasing).  digests receives count * ZK_DIGEST_BYTES bytes, digest i at byte
+ * 32 i, in the order hexdigest() prints them; the device array must be 4-byte aligned.  THE DIGEST, a stored format from here on:
+ *   ZK_DIGEST_SHA256        FIPS 180-4 SHA-256 of the frame's bytes.  The empty frame gives e3b0c442 98fc1c14 9afbf4c8 996fb924 27ae41e4 649b934c
+ *                           a495991b 7852b855.
+ *   ZK_DIGEST_BLAKE2S_TREE  BLAKE2s (RFC 7693) with the tree parameters of the BLAKE2 specification: digest length 32, no key, no salt, no
+ *                           personalisation, fanout 0 (unlimited), maximal depth 2, leaf length ZK_DIGEST_LEAF = 4096, inner length 32.  The
+ *                           frame is cut into n = max(1, ceil(len / 4096)) leaves; leaf k is hashed with node offset k and node depth 0, the
+ *                           last leaf carries the last-node flag, an empty frame has one empty leaf; the digest is the root: BLAKE2s over the
+ *                           n concatenated 32-byte leaf digests with node offset 0, node depth 1 and the last-node flag.  In Python:
+ *                               def tree(m, L=4096):
+ *                                   n = max(1, -(-len(m) // L))
+ *                                   inner = b"".join(hashlib.blake2s(m[k*L:(k+1)*L], digest_size=32, fanout=0, depth=2, leaf_size=L, node_offset=k,
+ *                                                    node_depth=0, inner_size=32, last_node=(k == n-1)).digest() for k in range(n))
+ *                                   return hashlib.blake2s(inner, digest_size=32, fanout=0, depth=2, leaf_size=L, node_offset=0, node_depth=1,
+ *                                                          inner_size=32, last_node=True).digest()
+ *                           The empty frame gives f516be67ca647aaa6b225e5844e35af8e4a7073cd445f0a41b3ba2a5d0584aa4, the 4097 bytes i & 255 give
+ *                           66d4770bed3555ad5838c35af7753df322a55172a6309c3a949d06919122f201.
+ * SHA-256 is the interoperable one (borg, restic, casync and OCI address chunks by it): a frame is ONE chain in one lane, fast for lists of
+ * short chunks and bound by that chain for long frames (2 MiB are 32 768 compressions one after the other).  The tree runs a lane per leaf, at
+ * device speed for any frame length; only the root of a very long frame is a chain again (a 1 GiB frame has 262 144 leaves, its root hashes
+ * 8 MiB in one lane).  Measured on 1 GiB of text cut at avg_size 4 KiB / 64 KiB / 2 MiB (tools/digest_probe.py, profiles/digest_probe.txt): the
+ * tree 1.58 / 0.89 / 4.06 ms -- at 2 MiB 3.6 ms of it the roots, the longest frame's 2 048 leaf digests in one lane --, SHA-256 3.92 / 20.8 /
+ * 729 ms: the 411 chains of the 2 MiB list run at 1.5 GB/s, below one host core.
+ * zk_frame_digests[_dev]:
+ *   - an unknown algo is ZK_ERR_ARGUMENT, returned before anything is read
+ *   - list errors, count == 0, count > ZK_SEEKABLE_MAX_FRAMES and NULL pointers as for zk_frame_keys[_dev]; a misaligned d_digests is
+ *     ZK_ERR_ARGUMENT; a refused call writes nothing
+ *   - nothing is stored outside d_digests[0, 32 count), nothing is loaded outside src[off[0], off[count])
+ *   - the device form SYNCHRONISES ITS STREAM once for the offsets and once at the end, as zk_frame_keys_dev does
+ * zk_archive_digests_dev: the digests of the DECODED content of archive frames [first, first + count) (d_comp, comp_size, d_c_off, d_d_off: what
+ * zk_decode_frame_list_dev reads).  The frames are decoded on context 0 exactly as zk_dedup_index_add_archive_dev decodes them -- checksums
+ * verified, against the engine's dictionary if one is set, in passes of at most ZK_CHOICE_DEDUP_PASS_KIB and at least one whole frame -- into
+ * engine scratch, and each pass is digested there by the same kernels behind the decode.  An entry of decoded size 0 gets the empty digest.  A
+ * frame that fails returns its -(code); the contents of d_digests[0, 32 count) are unspecified then, and nothing outside that range is written.
+ * The call does not know how many entries the tables hold: first + count above ZK_SEEKABLE_MAX_FRAMES, a decreasing d_d_off and frames that
+ * reach beyond comp_size are ZK_ERR_ARGUMENT.  It is refused while context 0 holds a submitted batch (the table above zk_decode_submit_dev).
+ * Not here: a digest-keyed index or a missing(digests) lookup, digests stored in a skippable frame or any on-disk container, keyed or salted
+ * hashing, SHA-512, BLAKE3, Level-B handles, a host-pointer form of the archive call. */
+#define ZK_DIGEST_SHA256        1
+#define ZK_DIGEST_BLAKE2S_TREE  2
+#define ZK_DIGEST_BYTES         32
+#define ZK_DIGEST_LEAF          4096
+int zk_frame_digests_dev(zk_engine *e, int algo, const void *d_src, const void *d_off, uint32_t count, void *d_digests, void *stream);
+int zk_frame_digests(zk_engine *e, int algo, const uint8_t *src, const uint64_t *off, uint32_t count, uint8_t *digests);
+int zk_archive_digests_dev(zk_engine *e, int algo, const void *d_comp, uint64_t comp_size, const void *d_c_off, const void *d_d_off,
+                           uint32_t first, uint32_t count, void *d_digests, void *stream);
 
 /* Host memory the host-pointer entry points above move by DMA directly (pinned; hipHostMalloc underneath).  Buffers from
  * anywhere else work too: they are staged through the engine's own pinned rings by worker threads, chunk by chunk, beside

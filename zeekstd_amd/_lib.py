@@ -141,6 +141,9 @@ _sig = {
     "zk_compact_archive_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _P]),
     "zk_remap_ids_dev": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, _P]),
     "zk_dedup_index_compact_dev": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "zk_frame_digests_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32, _P, _P]),
+    "zk_frame_digests": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32, _P]),
+    "zk_archive_digests_dev": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "zk_set_collective_library": (C.c_int, [C.c_char_p]),
     "zk_gather_seekable": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_int, _P, C.c_uint64, _P, _P, _P]),
 }

@@ -14,7 +14,8 @@ enum { ZK_K_WALK_COUNT = 0, ZK_K_SCAN, ZK_K_WALK_FILL, ZK_K_HUF, ZK_K_FSE, ZK_K_
        ZK_K_DEDUP_HASH, ZK_K_DEDUP_INSERT, ZK_K_DEDUP_VERIFY, ZK_K_DEDUP_VERIFY_LONG, ZK_K_DEDUP_COMPACT, ZK_K_DEDUP_GATHER,
        ZK_K_DXI_INSERT, ZK_K_DXI_LOOKUP, ZK_K_DXI_COMPARE, ZK_K_DXI_EMIT,
        ZK_K_CMP_MARK, ZK_K_CMP_EMIT, ZK_K_CMP_MOVE, ZK_K_CMP_REMAP, ZK_K_CMP_TAKE,
-       ZK_K_VIEW_PLAN, ZK_K_VIEW_MARK, ZK_K_VIEW_GATHER, ZK_K_VIEW_STATUS, ZK_NKERNELS };
+       ZK_K_VIEW_PLAN, ZK_K_VIEW_MARK, ZK_K_VIEW_GATHER, ZK_K_VIEW_STATUS,
+       ZK_K_DIGEST_PLAN, ZK_K_DIGEST_LEAVES, ZK_K_DIGEST_ROOTS, ZK_NKERNELS };
 
 struct zk_devbuf { void *p = nullptr; size_t cap = 0; };
 enum { ZK_MAX_CTX = 6 };
@@ -95,6 +96,7 @@ struct zk_engine {
         uint8_t *pin_dd = nullptr; size_t pin_dd_cap = 0;     // ... the caller's offsets and the unique frames' indices, brought to the host
         zk_devbuf dx;                       // zk_dedup_against_dev / zk_encode_dedup_against_dev (zk_dedup_index.hip): the lookup's scratch (ZkDxLayout); the decoded candidates of a pass lie in dctx[0].rng
         zk_devbuf cmp, cmp_gaps, cmp_stage; // zk_compact_archive_dev and its siblings (zk_compact.hip): the scratch (ZkCmpLayout); the gaps of an in-place compaction's steps; a staged step's bytes
+        zk_devbuf dg, dg_up;                // zk_frame_digests* / zk_archive_digests_dev (zk_digest.hip): the leaf counts, their prefix sums and the leaf digests (ZkgLayout); the host entry point's upload of source and offsets, and its digests
         int plan_choice = 0;                // ZK_CHOICE_ENC_PLAN
         uint32_t dedup_key_bits = 0;        // zk_dedup_frames*: bits of a frame's key that are kept (0 = all 64), ZK_CHOICE_DEDUP_KEY_BITS
         uint64_t dedup_slice_bytes = 0;     // zk_encode_dedup*: bytes of unique frames gathered and encoded at a time (0 = 1 GiB), ZK_CHOICE_DEDUP_SLICE_KIB

@@ -102,7 +102,8 @@ extern "C" const char *zk_engine_kernel_name(int k)
                                              "zk_k_dedup_hash", "zk_k_dedup_insert", "zk_k_dedup_verify", "zk_k_dedup_verify_long", "zk_k_dedup_compact", "zk_k_dedup_gather",
                                              "zk_k_dxi_insert", "zk_k_dxi_lookup", "zk_k_dxi_compare", "zk_k_dxi_emit",
                                              "zk_k_cmp_mark", "zk_k_cmp_emit", "zk_k_cmp_move", "zk_k_cmp_remap_ids", "zk_k_cmp_take",
-                                             "zk_k_view_plan", "zk_k_view_mark", "zk_k_view_gather", "zk_k_view_status"};
+                                             "zk_k_view_plan", "zk_k_view_mark", "zk_k_view_gather", "zk_k_view_status",
+                                             "zk_k_digest_plan", "zk_k_digest_leaves", "zk_k_digest_roots"};
     return k >= 0 && k < ZK_NKERNELS ? names[k] : "";
 }
 extern "C" int zk_engine_kernel_times(const zk_engine *e, float *ms_out, int n)
@@ -185,7 +186,7 @@ extern "C" void zk_engine_destroy(zk_engine *e)
     for (auto &c : e->dctx) if (c.st) (void)hipStreamSynchronize(c.st);
     zk_devbuf *bufs[] = {&e->dict.buf, &e->st_prefix, &e->st_comp, &e->st_off, &e->st_dst, &e->st_misc, &e->rf_entries, &e->rf_frames,
                          &e->enc.lists, &e->enc.seqs, &e->enc.lits, &e->enc.scratch, &e->enc.words, &e->enc.ftab, &e->enc.hist, &e->enc.seg, &e->enc.ldm, &e->enc.dense, &e->enc.plan, &e->enc.train, &e->enc.train_src, &e->enc.cdc, &e->enc.cdc_src, &e->enc.cdc_off,
-                         &e->enc.dd, &e->enc.dd_src, &e->enc.dd_off, &e->enc.dd_dry, &e->enc.dd_up, &e->enc.dd_out, &e->enc.dx, &e->enc.cmp, &e->enc.cmp_gaps, &e->enc.cmp_stage};
+                         &e->enc.dd, &e->enc.dd_src, &e->enc.dd_off, &e->enc.dd_dry, &e->enc.dd_up, &e->enc.dd_out, &e->enc.dx, &e->enc.cmp, &e->enc.cmp_gaps, &e->enc.cmp_stage, &e->enc.dg, &e->enc.dg_up};
     for (zk_devbuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (e->h_words) (void)hipHostFree(e->h_words);
     for (int k = 0; k < ZK_NKERNELS; k++) { if (e->ev_start[k]) (void)hipEventDestroy(e->ev_start[k]); if (e->ev_stop[k]) (void)hipEventDestroy(e->ev_stop[k]); }

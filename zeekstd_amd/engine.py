@@ -468,6 +468,43 @@ class Engine:
         if rc != 0:
             self._raise(rc)
 
+    DIGESTS = {"sha256": 1, "blake2s-tree": 2}              # ZK_DIGEST_SHA256, ZK_DIGEST_BLAKE2S_TREE
+
+    @classmethod
+    def _digest_algo(cls, algo):
+        if algo not in cls.DIGESTS:
+            raise ValueError("algo must be one of %s" % ", ".join(sorted(cls.DIGESTS)))
+        return cls.DIGESTS[algo]
+
+    def frame_digests(self, data, offsets, algo="sha256"):
+        """zk_frame_digests: the digest of every frame of `data` (cut by `offsets`), algo "sha256" or "blake2s-tree" (the tree of
+        include/zeekstd_amd.h, leaves of 4096 bytes) -> np.uint8[count, 32], a row's bytes in the order hexdigest() prints them"""
+        code = self._digest_algo(algo)
+        data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        off = _u64(offsets)
+        count = max(len(off) - 1, 0)
+        out = np.zeros((max(count, 1), 32), np.uint8)
+        rc = lib.zk_frame_digests(self._h, code, data.ctypes.data if data.size else None, off.ctypes.data, count, out.ctypes.data)
+        if rc != 0:
+            self._raise(rc)
+        return out[:count]
+
+    def frame_digests_dev(self, d_src, d_off, count, d_digests, algo="sha256", stream=None):
+        """zk_frame_digests_dev: device tensors (or raw pointers); d_digests: 32 * count bytes, 4-byte aligned"""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        rc = lib.zk_frame_digests_dev(self._h, self._digest_algo(algo), opt(d_src), opt(d_off), count, opt(d_digests), stream)
+        if rc != 0:
+            self._raise(rc)
+
+    def archive_digests_dev(self, d_comp, comp_size, d_c_off, d_d_off, first, count, d_digests, algo="sha256", stream=None):
+        """zk_archive_digests_dev: the digests of the decoded content of archive frames [first, first + count) -> d_digests (32 * count bytes,
+        4-byte aligned).  Returns 0 or -(code) of a frame that failed to decode or verify"""
+        opt = lambda t: self._ptr(t) if t is not None else None
+        rc = lib.zk_archive_digests_dev(self._h, self._digest_algo(algo), opt(d_comp), comp_size, opt(d_c_off), opt(d_d_off), first, count, opt(d_digests), stream)
+        if rc <= -1000:
+            self._raise(rc)
+        return rc
+
     def dedup_against_dev(self, index, d_comp, comp_size, d_c_off, d_d_off, n_frames, d_src, d_off, count, d_ids=None, d_fresh=None, stream=None):
         """zk_dedup_against_dev: which frames of the list the archive (d_comp, d_c_off, d_d_off, n_frames; known to `index`) already holds.
         d_ids / d_fresh: uint32 device arrays of `count` entries, or None.  Returns n_fresh."""
@@ -842,6 +879,22 @@ class DedupStore:
             self.engine._raise(rc)
         out = dst[:n].cpu().numpy()
         return [out[int(at[i]):int(at[i + 1])].tobytes() for i in range(count)]
+
+    def digests(self, first=0, count=None, algo="sha256"):
+        """the digests of the stored chunks [first, first + count) (count None: to the end), of their decoded content -> np.uint8[count, 32]
+        (archive_digests_dev over the store's own buffers).  A chunk that does not decode raises."""
+        import torch
+        count = self.n_frames - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.n_frames:
+            raise ValueError("chunks [%d, %d) are not in a store of %d" % (first, first + count, self.n_frames))
+        if count == 0:
+            return np.zeros((0, 32), np.uint8)
+        out = torch.zeros(count * 32, dtype=torch.uint8, device=self._dev)
+        torch.cuda.synchronize()
+        rc = self.engine.archive_digests_dev(self._comp, self.comp_size, self._dev_u64(self._c_off), self._dev_u64(self._d_off), first, count, out, algo)
+        if rc != 0:
+            self.engine._raise(rc)
+        return out.cpu().numpy().reshape(count, 32)
 
     def compact(self, keep):
         """Drops every chunk that none of the snapshots in `keep` (a list of `ids` arrays, as append returned them) uses: the archive is
